@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- filter-function elements/s on BASELINE.json config 2, 1..8 GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full pass of the hot path over one pulse, HBM-resident in and out: Hamiltonian ->
@@ -18,11 +18,19 @@ period the part needs ~300 steps (35 ms) to reach its sustained clocks (profiles
 `--steps 20 --warmup 5` run never gets to on its own.
 
 Rank 0 prints ONE JSON line.  value = elements/s over all ranks, element count
-E = n_seg * n_omega_total * n_nops * d^2 per step (BASELINE.json metric).  Besides the contract
-keys the line carries `roofline` (+ `frac_step`), `cpu_baseline`, `api_call_ms` (the user-facing
-PulseSequence.get_filter_function + ff.infidelity call on host arrays) and `configs`: BASELINE
-configs 3, 4 (one rank's shard; with N > 1 the whole 65536-omega grid strong-scaled over the ranks)
-and 5, each timed in-process after the headline.
+E = n_seg * n_omega_total * n_nops * d^2 per step (BASELINE.json metric); ms_per_step = the wall
+time of the K timed steps / K.  Besides the contract keys the line carries `roofline` (+
+`frac_step`, from the HIP events of the timed region).  A plain run measures nothing else.  With
+--full it also carries `cpu_baseline` + `parity` (the oracle on the same inputs), the PMC traffic,
+`api_call_ms` (the user-facing PulseSequence.get_filter_function + ff.infidelity call on host
+arrays), `single_stream_ms_per_step` and `configs`: BASELINE configs 3, 4 (one rank's shard; with
+N > 1 the whole 65536-omega grid strong-scaled over the ranks) and 5, each timed in-process after
+the headline.
+
+--dump-outputs DIR writes what the last timed step computed -- rank 0's infidelities, filter
+function and control matrix -- as float64 DIR/<name>.npy (complex arrays with a trailing axis of
+2: real, imaginary), at most 60 MiB in all (beyond that a fixed, seeded sample of the frequencies).
+The inputs depend on the arguments alone (seeded), so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -758,6 +766,29 @@ def bench_api_call(ff, c_opers, c_coeffs, n_opers, n_coeffs, dt, basis, omega, s
                 infidelity_on_fresh_pulse_ms=float(np.median(t_one)*1e3)), infid
 
 
+# ---- --dump-outputs ----------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 60 << 20
+
+
+def dump_outputs(directory, arrays, omega_axis, limit=DUMP_LIMIT_BYTES):
+    """Write every array as float64 to directory/<name>.npy.  Should they exceed `limit` bytes together,
+    the arrays named in `omega_axis` (name -> axis) keep the same fixed, seeded sample of their
+    frequency indices, in ascending order.  Returns the bytes written (without the .npy headers)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        fixed = sum(a.nbytes for k, a in arrays.items() if k not in omega_axis)
+        per_omega = sum(a.nbytes//a.shape[omega_axis[k]] for k, a in arrays.items() if k in omega_axis)
+        n_omega = min(arrays[k].shape[ax] for k, ax in omega_axis.items())
+        keep = int(min(n_omega, max(1, (limit - fixed)//per_omega)))
+        idx = np.sort(np.random.default_rng(0).choice(n_omega, size=keep, replace=False))
+        arrays = {k: np.take(a, idx, axis=omega_axis[k]) if k in omega_axis else a for k, a in arrays.items()}
+        print(f'bench.py: outputs sampled at {keep} of {n_omega} frequencies (seed 0)', file=sys.stderr)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + '.npy'), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 GPU_MODULES = ('torch', 'filter_functions_amd')
 
 
@@ -922,12 +953,24 @@ def main():
                     help='enqueue every step call by call instead of replaying captured hipGraphs')
     ap.add_argument('--no-prewarm', action='store_true')
     ap.add_argument('--published-example', action='store_true',
-                    help='also time the reference notebook periodic_driving (outside the hot-path scope)')
+                    help='with --full: also time the reference notebook periodic_driving (outside the '
+                         'hot-path scope)')
     ap.add_argument('--prewarm-max-s', type=float, default=1.0)
     ap.add_argument('--child', action='store_true',
                     help='profiler child run: headline loop only, no baseline / PMC / configs')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline figure: CPU baseline and parity, PMC '
+                         'traffic, configs 3-5 and the other dimensions, the user-facing call, the '
+                         'single-stream latency, extra instrumented launches, the gather A/B (N > 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (infidelity, filter function, control '
+                         'matrix; complex arrays as float64 (..., 2)) to DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.child:
+        args.full = False
+    if not args.full:
         args.no_cpu_baseline = args.no_pmc = args.no_configs = True
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python3 bench.py --gpus N` as the driver types it: this process becomes the launcher and
@@ -1034,7 +1077,7 @@ def main():
     # a short timed region (the driver's --steps 20) instruments 3 launches only: further launches
     # of the same schedule are instrumented right AFTER the closing bracket (untimed steps, queue
     # kept full by a few plain steps first) so that the mean is over at least 8 launches
-    n_extra = max(0, 8 - n_ev)
+    n_extra = max(0, 8 - n_ev) if args.full else 0
     lead_extra = 1 if (n_extra and max(1, args.streams) > 1) else 0
     timer = AccumulateTimer(lib, _lib, n_ev + lead + n_extra + lead_extra)
 
@@ -1053,6 +1096,16 @@ def main():
 
     def sync():
         torch.cuda.synchronize(device)
+
+    outputs = {}
+
+    def last_step_outputs(infid):
+        """Host copies of what the last timed step computed: its infidelities and the filter function and
+        control matrix of the buffer set it wrote (this rank's omega block)."""
+        src = ring.pipes[(ring.count - 1) % ring.depth] if use_ring else pipe
+        return {'infidelity': infid.cpu().numpy(),
+                'filter_function': torch.view_as_real(src.filter_function).cpu().numpy(),
+                'control_matrix': torch.view_as_real(src.control_matrix).cpu().numpy()}
 
     def measure():
         """Pre-warm, W warm-up steps, then EXACTLY K timed steps bracketed by barrier + synchronize."""
@@ -1076,6 +1129,8 @@ def main():
         torch.cuda.synchronize(device)
         total = time.perf_counter() - t0
         timer.disarm()
+        if args.dump_outputs:
+            outputs.update(last_step_outputs(last))
         if n_extra:
             for _ in range(2*depth):
                 step()
@@ -1122,7 +1177,7 @@ def main():
             push_error_word = int(word.item())
     pipe.check_status()                          # eigensolver flags of the device-resident run
     all_gather_measured = None
-    if use_dist:
+    if use_dist and args.full:
         # the collective alone at the headline's block size and at config 4's per-rank size: what `scaling_model`
         # assumes (76.5 GB/s per link and direction, 25 us) against what this node does
         all_gather_measured = measure_all_gather(torch, dist, device, world, rank,
@@ -1130,7 +1185,7 @@ def main():
     gather_ab = {'fallback': gather_fallback} if gather_fallback else None
     if gather_fallback:
         os.environ['FFK_GATHER'] = 'rccl'        # the strong-scaled configs below follow suit
-    if use_dist and not gather_fallback:
+    if use_dist and args.full and not gather_fallback:
         # the other gather method on the same workload, 200 steps, for the record
         other = 'rccl' if ring.gather == 'push' else 'push'
         try:
@@ -1157,7 +1212,7 @@ def main():
             gather_ab = {'headline': ring.gather, other: f'failed: {err}'}
     # latency of one pass on its own (one stream, nothing else in flight), for reference
     latency_ms = None
-    if not use_dist:
+    if not use_dist and args.full:
         one = stream
         torch.cuda.synchronize(device)
         reps = 200
@@ -1307,7 +1362,7 @@ def main():
             out['all_gather_measured'] = all_gather_measured
         if world == 1:      # the model extrapolates from what ONE GPU measures
             out['scaling_model'] = scaling_model(elapsed/args.steps*1e3, A*A*args.omega_per_gpu*16, configs)
-        if world == 1 and not args.child:
+        if world == 1 and args.full:
             api, infid_api = bench_api_call(ff, c_opers, c_coeffs, n_opers, n_coeffs, dt, basis, omega,
                                             spectrum_full)
             out.update(api)
@@ -1329,6 +1384,8 @@ def main():
                                                     / np.abs(infid_ref).max()),
                 'against': 'oracle (NumPy restatement of the reference), same inputs',
             }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs, omega_axis={'filter_function': -2, 'control_matrix': -2})
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

@@ -5,7 +5,7 @@
 rounds=$1; shift
 for r in $(seq $rounds); do
   for e in "$@"; do
-    line=$(env $e python3 bench.py --no-configs --no-pmc --no-cpu-baseline 2>/dev/null | tail -1)
+    line=$(env $e python3 bench.py --full --no-configs --no-pmc --no-cpu-baseline 2>/dev/null | tail -1)
     python3 - "$e" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])

@@ -6,6 +6,5 @@
 #   python -m pytest tests/test_sanitizer_build.py -q        (or: tools/run_asan_checks.sh)
 set -e
 cd "$(dirname "$0")/.."
-make -C filter_functions_amd/csrc -j"${JOBS:-6}" VARIANT=asan \
-  VFLAGS="-fsanitize=address,undefined -fno-gpu-sanitize -shared-libasan -fno-omit-frame-pointer -g -O1 -DFFK_HOST_SANITIZE" \
-  HIPCC_LINK_FLAGS="-fsanitize=address,undefined -shared-libasan"
+# one line, so that the sanitizer options and the switch that keeps them off the device code stay together
+make -C filter_functions_amd/csrc -j"${JOBS:-6}" VARIANT=asan VFLAGS="-fsanitize=address,undefined -fno-gpu-sanitize -shared-libasan -fno-omit-frame-pointer -g -O1 -DFFK_HOST_SANITIZE" HIPCC_LINK_FLAGS="-fsanitize=address,undefined -fno-gpu-sanitize -shared-libasan"

@@ -200,6 +200,12 @@ SIGNATURES = {
                                  c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
     'ffk_eigensolver_status_dev': (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    'ffk_pipeline_batch_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'ffk_pipeline_batch_dev': (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+    'ffk_eigensolver_status_batch_dev': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ffk_kernel_fault_status': (c_int, [POINTER(c_int32), c_int]),
     'ffk_resident_create': (c_int, [POINTER(c_void_p)]),
     'ffk_resident_destroy': (c_int, [c_void_p]),
@@ -225,6 +231,13 @@ SIGNATURES = {
                                                         POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     'ffk_resident_infidelity': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                         c_void_p]),
+    'ffk_resident_batch_filter_function_infidelity': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                              c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                                              c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                                              c_int, c_void_p, c_int, c_int, POINTER(c_void_p),
+                                                              POINTER(c_void_p), POINTER(c_void_p),
+                                                              POINTER(c_void_p), c_void_p, c_void_p]),
+    'ffk_resident_batch_control_matrix': (c_int, [c_void_p, c_int, c_void_p]),
     'ffk_ipc_get_handle': (c_int, [c_void_p, c_void_p]),
     'ffk_ipc_open_handle': (c_int, [c_void_p, POINTER(c_void_p)]),
     'ffk_ipc_close_handle': (c_int, [c_void_p]),

@@ -769,6 +769,14 @@ void set_use_wave_kernel(bool on) { g_use_wave_kernel = on; }
 void set_use_gsplit(bool on) { g_use_gsplit = on; }
 void set_mfma_policy(int policy) { g_mfma_policy = policy; }
 
+AccumGeometry accumulate_geometry_pulses(int W, int A, int G, int d, int P) {
+    const int single = accumulate_geometry(W, A, G, d, 0).chunks;
+    int per_pulse = std::max(1, single/std::max(1, P));
+    while (G % per_pulse != 0) --per_pulse;
+    const AccumGeometry geo = accumulate_geometry(W, A, P*G, d, P*per_pulse);
+    return geo;     // (chunk_len = G/per_pulse, chunks = P per_pulse: P G/(P per_pulse) is exact)
+}
+
 AccumGeometry accumulate_geometry(int W, int A, int G, int d, int forced_chunks) {
     AccumGeometry geo;
     geo.gsplit = 1;

@@ -340,6 +340,73 @@ __global__ __launch_bounds__(64) void eigh_expm_controls_kernel(const cplx* __re
     }
 }
 
+// Batched form (ffk_pipeline_batch_dev): P pulses of G segments each, pulse-major, block (segment, pulse); every
+// pulse has its own control operators (P, n_c, D, D) and amplitudes (P, n_c, G).  Same sums, same FMAs as the
+// kernel above.
+template <int D>
+__global__ __launch_bounds__(64) void eigh_expm_controls_pulses_kernel(const cplx* __restrict__ opers,
+                                                                       const double* __restrict__ coeffs, int n_c,
+                                                                       const double* __restrict__ dt, int G,
+                                                                       double* __restrict__ eigvals,
+                                                                       cplx* __restrict__ eigvecs,
+                                                                       cplx* __restrict__ seg_prop,
+                                                                       int* __restrict__ status) {
+    __shared__ EighState<D> st;
+    __shared__ cplx Hs[D*D];
+    __builtin_amdgcn_s_setprio(3);     // see ffk_internal.h FFK_SMALL_KERNEL_PRIORITY
+    const int g = blockIdx.x;
+    const size_t p = blockIdx.y, pg = p*G + g;
+    const int lane = threadIdx.x;
+    const cplx* op = opers + p*n_c*D*D;
+    const double* co = coeffs + p*n_c*G;
+    for (int e = lane; e < D*D; e += 64) {
+        cplx acc = {0.0, 0.0};
+        for (int i = 0; i < n_c; ++i) {
+            const double c = co[static_cast<size_t>(i)*G + g];
+            const cplx o = op[i*D*D + e];
+            acc.re = fma(c, o.re, acc.re);
+            acc.im = fma(c, o.im, acc.im);
+        }
+        Hs[e] = acc;
+    }
+    wave_sync();
+    const bool ok = eigh_expm_wave<D>(st, Hs, dt[pg], lane, eigvals + pg*D, eigvecs + pg*D*D, seg_prop + pg*D*D);
+    if (lane == 0) status[pg] = ok ? 0 : 1;
+}
+
+// H (P, G, d, d) from per-pulse controls, the sum of the kernels above (the batch entry's route for the shapes that
+// run single passes)
+__global__ __launch_bounds__(256) void assemble_hamiltonians_pulses_kernel(const cplx* __restrict__ opers, const double* __restrict__ coeffs,
+                                                    int n_c, int G, int dd, size_t n, cplx* __restrict__ H) {
+    const size_t e = static_cast<size_t>(blockIdx.x)*blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const size_t pg = e / dd;
+    const size_t p = pg / G;
+    const int g = static_cast<int>(pg % G), k = static_cast<int>(e % dd);
+    cplx acc = {0.0, 0.0};
+    for (int i = 0; i < n_c; ++i) {
+        const double c = coeffs[(p*n_c + i)*G + g];
+        const cplx o = opers[(p*n_c + i)*dd + k];
+        acc.re = fma(c, o.re, acc.re);
+        acc.im = fma(c, o.im, acc.im);
+    }
+    H[e] = acc;
+}
+
+// out[p] = number of flagged segments of pulse p (one block per pulse; every block writes its word)
+__global__ __launch_bounds__(256) void count_failures_pulses_kernel(const int* __restrict__ status, int G,
+                                                                    int32_t* __restrict__ out) {
+    __shared__ int total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const int* sp = status + static_cast<size_t>(blockIdx.x)*G;
+    int mine = 0;
+    for (int g = threadIdx.x; g < G; g += blockDim.x) mine += sp[g] != 0;
+    if (mine) atomicAdd(&total, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = total;
+}
+
 template <int D>
 hipError_t launch_d(const cplx* H, const double* dt, int G, double* eigvals, cplx* eigvecs,
                     cplx* seg_prop, int* status, int* fail_count, hipStream_t stream) {
@@ -391,6 +458,38 @@ hipError_t launch_eigh_expm_controls(const cplx* opers, const double* coeffs, in
         default:
             return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_eigh_expm_controls_pulses(const cplx* opers, const double* coeffs, int n_c, const double* dt,
+                                            int G, int P, int d, double* eigvals, cplx* eigvecs, cplx* seg_prop,
+                                            int* status, hipStream_t stream) {
+    if (P < 1 || P > 65535) return hipErrorInvalidValue;
+    switch (d) {
+#define FFK_CASE(D)                                                                                          \
+    case D:                                                                                                  \
+        hipLaunchKernelGGL(eigh_expm_controls_pulses_kernel<D>, dim3(G, P), dim3(64), 0, stream, opers,      \
+                           coeffs, n_c, dt, G, eigvals, eigvecs, seg_prop, status);                          \
+        return hipGetLastError();
+        FFK_CASE(2) FFK_CASE(3) FFK_CASE(4) FFK_CASE(5) FFK_CASE(6) FFK_CASE(7) FFK_CASE(8)
+        FFK_CASE(9) FFK_CASE(10) FFK_CASE(11) FFK_CASE(12) FFK_CASE(13) FFK_CASE(14)
+        FFK_CASE(15) FFK_CASE(16)
+#undef FFK_CASE
+        default:
+            return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_assemble_hamiltonians_pulses(const cplx* opers, const double* coeffs, int n_c, int G, int P, int d,
+                                               cplx* H, hipStream_t stream) {
+    const size_t n = static_cast<size_t>(P)*G*d*d;
+    hipLaunchKernelGGL(assemble_hamiltonians_pulses_kernel, dim3(static_cast<unsigned>((n + 255)/256)), dim3(256), 0,
+                       stream, opers, coeffs, n_c, G, d*d, n, H);
+    return hipGetLastError();
+}
+
+hipError_t launch_count_failures_pulses(const int* status, int G, int P, int32_t* out, hipStream_t stream) {
+    hipLaunchKernelGGL(count_failures_pulses_kernel, dim3(P), dim3(256), 0, stream, status, G, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_eigh_expm(const cplx* H, const double* dt, int G, int d, double* eigvals,

@@ -133,6 +133,14 @@ int pipeline_dev_impl(const double* hamiltonian, const double* dt, const double*
                       double* filter_function, double* infid, void* workspace, size_t workspace_bytes,
                       void* stream, PassOptions& opt);
 
+// ffk_api_batch.hip: ffk_pipeline_batch_dev with the integral's dimension given apart (the resident batch pass)
+int pipeline_batch_dev_impl(int P, const double* c_opers, int n_cops, const double* c_coeffs, const double* dt,
+                            const double* t, int G, int d, const double* omega, int W, const double* basis, int N,
+                            const double* n_opers, int A, const double* n_coeffs, const double* spectrum, int s_ndim,
+                            const int32_t* idx, int n_idx, int d_infidelity, double* eigvals, double* eigvecs,
+                            double* propagators, double* control_matrix, double* filter_function, double* infid,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 // Scratch from the shared arena is handed to kernels on a non-blocking stream while g_arena.mu is
 // held; the lock may only be dropped once that stream has drained -- on EVERY exit path, also the
 // early error returns after the first enqueue: the next holder may reuse or reallocate

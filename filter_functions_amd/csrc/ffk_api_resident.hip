@@ -121,6 +121,11 @@ struct ffk_resident {
     bool valid = false;
     Block dev = {nullptr, 0, -1}, pin = {nullptr, 0, -1};
     ResidentLayout L = {};
+    // a batched pass (ffk_resident_batch_filter_function_infidelity) leaves `valid` false: the single-pulse readers
+    // do not apply to it
+    int P = 0;
+    bool batch_valid = false;
+    size_t batch_R = 0;           // device offset of the control matrices (P, A, N, W)
 };
 
 extern "C" {
@@ -634,6 +639,126 @@ int ffk_resident_control_matrix(ffk_resident* r, double* control_matrix) {
     const unsigned char* dp = static_cast<const unsigned char*>(r->dev.ptr);
     FFK_HIP(hipMemcpyAsync(control_matrix, dp + r->L.R, 16*size_t(r->A)*r->N*r->W,
                            hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    return FFK_OK;
+}
+
+int ffk_resident_batch_filter_function_infidelity(ffk_resident* r, int P, const double* c_opers, int n_c,
+                                                  const double* c_coeffs, const double* dt, const double* t, int G,
+                                                  int d, const double* omega, int W, const double* basis, int N,
+                                                  const double* n_opers, int A, const double* n_coeffs,
+                                                  const double* spectrum, int s_ndim, int spectrum_is_real,
+                                                  const int32_t* idx, int n_idx, int d_inf, double** eigvals,
+                                                  double** eigvecs, double** propagators, double** filter_function,
+                                                  double* infid, int32_t* n_failed) {
+    FFK_REQUIRE(r, "NULL handle");
+    FFK_REQUIRE(P >= 1 && P <= 65535, "need 1 <= P <= 65535 pulses, got P=%d", P);
+    FFK_REQUIRE(d_templated_ok(d), "unsupported dimension d=%d (need 2 <= d <= %d)", d, FFK_MAX_D_TEMPLATED);
+    FFK_REQUIRE(W >= 1 && N >= 1 && A >= 1 && G >= 1 && n_c >= 1, "empty axis: W=%d N=%d A=%d G=%d n_cops=%d", W, N,
+                A, G, n_c);
+    FFK_REQUIRE(c_opers && c_coeffs && dt && t && omega && basis && n_opers && n_coeffs, "NULL argument");
+    FFK_REQUIRE(eigvals && eigvecs && propagators && filter_function && n_failed, "NULL output argument");
+    size_t s_rows = 0, n_out = 0;
+    if (spectrum) {
+        FFK_REQUIRE(idx && infid && s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= A && d_inf >= 1 && W >= 2,
+                    "bad spectrum arguments");
+        s_rows = s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx);
+        n_out = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
+    }
+    r->valid = r->batch_valid = false;
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    const size_t dd = size_t(d)*d, PG = size_t(P)*G;
+    // [inputs: one H2D][outputs: one D2H] in both blocks, then the control matrices on the device only
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    const size_t o_cop = put(16*size_t(P)*n_c*dd), o_cc = put(8*size_t(P)*n_c*G), o_dt = put(8*PG),
+                 o_t = put(8*size_t(P)*(G + 1)), o_om = put(8*size_t(W)), o_b = put(16*size_t(N)*dd),
+                 o_no = put(16*size_t(P)*A*dd), o_nc = put(8*size_t(P)*A*G), o_S = put(16*s_rows*W),
+                 o_idx = put(sizeof(int32_t)*size_t(n_idx)), inputs_end = o;
+    const size_t o_D = put(8*PG*d), o_V = put(16*PG*dd), o_Q = put(16*size_t(P)*(G + 1)*dd),
+                 o_F = put(16*size_t(P)*A*A*W), o_inf = put(8*size_t(P)*n_out), o_fail = put(sizeof(int32_t)*P),
+                 outputs_end = o;
+    const size_t o_R = put(16*size_t(P)*A*N*W), dev_end = o;
+    if (r->device != dev || r->dev.size < dev_end || r->pin.size < outputs_end) {
+        g_dev_pool.give(r->dev);
+        g_pin_pool.give(r->pin);
+        r->dev = r->pin = Block{nullptr, 0, -1};
+        if (int rc = g_dev_pool.take(dev_end, dev, &r->dev)) return rc;
+        if (int rc = g_pin_pool.take(outputs_end, dev, &r->pin)) return rc;
+        r->device = dev;
+    }
+    r->P = P; r->G = G; r->d = d; r->W = W; r->N = N; r->A = A; r->batch_R = o_R;
+    unsigned char* hp = static_cast<unsigned char*>(r->pin.ptr);
+    unsigned char* dp = static_cast<unsigned char*>(r->dev.ptr);
+    const auto clock0 = std::chrono::steady_clock::now();
+    std::memcpy(hp + o_cop, c_opers, 16*size_t(P)*n_c*dd);
+    std::memcpy(hp + o_cc, c_coeffs, 8*size_t(P)*n_c*G);
+    std::memcpy(hp + o_dt, dt, 8*PG);
+    std::memcpy(hp + o_t, t, 8*size_t(P)*(G + 1));
+    std::memcpy(hp + o_om, omega, 8*size_t(W));
+    std::memcpy(hp + o_b, basis, 16*size_t(N)*dd);
+    std::memcpy(hp + o_no, n_opers, 16*size_t(P)*A*dd);
+    std::memcpy(hp + o_nc, n_coeffs, 8*size_t(P)*A*G);
+    if (spectrum) {
+        double* hs = reinterpret_cast<double*>(hp + o_S);
+        if (spectrum_is_real) {
+            for (size_t i = 0; i < s_rows*W; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
+        } else {
+            std::memcpy(hs, spectrum, 16*s_rows*W);
+        }
+        std::memcpy(hp + o_idx, idx, sizeof(int32_t)*size_t(n_idx));
+    }
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    const size_t wsb = ffk_pipeline_batch_workspace_bytes(P, W, N, A, G, d, n_idx, s_ndim);
+    void* ws;
+    if (int rc = arena_reserve(wsb, &ws)) return rc;
+    StreamDrain drain{s};
+    const auto clock1 = std::chrono::steady_clock::now();
+    auto dptr = [dp](size_t off) { return reinterpret_cast<double*>(dp + off); };
+    FFK_HIP(hipMemcpyAsync(dp, hp, inputs_end, hipMemcpyHostToDevice, s));
+    if (int rc = pipeline_batch_dev_impl(P, dptr(o_cop), n_c, dptr(o_cc), dptr(o_dt), dptr(o_t), G, d, dptr(o_om), W,
+                                         dptr(o_b), N, dptr(o_no), A, dptr(o_nc), spectrum ? dptr(o_S) : nullptr,
+                                         s_ndim, reinterpret_cast<const int32_t*>(dp + o_idx), n_idx, d_inf,
+                                         dptr(o_D), dptr(o_V), dptr(o_Q), dptr(o_R), dptr(o_F),
+                                         spectrum ? dptr(o_inf) : nullptr, ws, wsb, s))
+        return rc;
+    if (int rc = ffk_eigensolver_status_batch_dev(ws, wsb, P, G, d, reinterpret_cast<int32_t*>(dp + o_fail), s))
+        return rc;
+    FFK_HIP(hipMemcpyAsync(hp + o_D, dp + o_D, outputs_end - o_D, hipMemcpyDeviceToHost, s));
+    const auto clock2 = std::chrono::steady_clock::now();
+    FFK_HIP(hipStreamSynchronize(s));
+    const auto clock3 = std::chrono::steady_clock::now();
+    r->t_stage = std::chrono::duration<double>(clock1 - clock0).count();
+    r->t_enqueue = std::chrono::duration<double>(clock2 - clock1).count();
+    r->t_wait = std::chrono::duration<double>(clock3 - clock2).count();
+    if (int rc = kernel_fault_status()) return rc;
+    std::memcpy(n_failed, hp + o_fail, sizeof(int32_t)*P);
+    for (int p = 0; p < P; ++p)
+        if (n_failed[p] != 0)
+            return fail(FFK_ENOCONV, "Jacobi eigensolver did not converge for %d segment(s) of pulse %d of the batch",
+                        int(n_failed[p]), p);
+    *eigvals = reinterpret_cast<double*>(hp + o_D);
+    *eigvecs = reinterpret_cast<double*>(hp + o_V);
+    *propagators = reinterpret_cast<double*>(hp + o_Q);
+    *filter_function = reinterpret_cast<double*>(hp + o_F);
+    if (spectrum) std::memcpy(infid, hp + o_inf, 8*size_t(P)*n_out);
+    r->batch_valid = true;
+    return FFK_OK;
+}
+
+int ffk_resident_batch_control_matrix(ffk_resident* r, int pulse, double* control_matrix) {
+    FFK_REQUIRE(r && r->batch_valid, "no resident batch result");
+    FFK_REQUIRE(control_matrix, "NULL argument");
+    FFK_REQUIRE(pulse >= 0 && pulse < r->P, "pulse %d out of range [0, %d)", pulse, r->P);
+    if (int rc = on_owning_device(r)) return rc;
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    const size_t bytes = 16*size_t(r->A)*r->N*r->W;
+    const unsigned char* dp = static_cast<const unsigned char*>(r->dev.ptr);
+    FFK_HIP(hipMemcpyAsync(control_matrix, dp + r->batch_R + size_t(pulse)*bytes, bytes, hipMemcpyDeviceToHost, s));
     FFK_HIP(hipStreamSynchronize(s));
     return FFK_OK;
 }

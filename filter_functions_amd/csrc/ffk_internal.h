@@ -64,6 +64,16 @@ hipError_t launch_eigh_expm_controls(const cplx* opers, const double* coeffs, in
                                      hipStream_t stream, int* fail_count = nullptr);
 // out[0] = number of non-zero entries of status (G): the device-resident paths' convergence check
 hipError_t launch_count_failures(const int* status, int G, int32_t* out, hipStream_t stream);
+// Batched forms (ffk_pipeline_batch_dev): P pulses of G segments, every array pulse-major (opers (P, n_c, d, d),
+// coeffs (P, n_c, G), dt (P, G); outputs (P, G, ...)); status (P, G) as above; grid (segment, pulse).
+hipError_t launch_eigh_expm_controls_pulses(const cplx* opers, const double* coeffs, int n_c, const double* dt,
+                                            int G, int P, int d, double* eigvals, cplx* eigvecs, cplx* seg_prop,
+                                            int* status, hipStream_t stream);
+// H (P, G, d, d) = sum_i coeffs[p, i, g] opers[p, i]
+hipError_t launch_assemble_hamiltonians_pulses(const cplx* opers, const double* coeffs, int n_c, int G, int P, int d,
+                                               cplx* H, hipStream_t stream);
+// out[p] = number of non-zero entries of status[p, :] (P, G); every word written, no memset needed
+hipError_t launch_count_failures_pulses(const int* status, int G, int P, int32_t* out, hipStream_t stream);
 // Chunk length of the two-kernel scan used by the fused front end (scan_local + fix-up fused
 // with the prologue): both serial parts are ~sqrt(G) long at G = 256.
 // FFK_SMALL_KERNEL_PRIORITY: the latency-bound kernels of a pass (eigensolver, scans, prologue,
@@ -99,6 +109,9 @@ size_t scan_workspace_bytes(int G, int d);
 // chunk-local prefix products Qloc (G+1,d,d) (Qloc[0] = 1) and chunk totals (nchunks,d,d)
 hipError_t launch_scan_local(const cplx* seg_prop, int G, int d, int L, cplx* Qloc, cplx* totals,
                              hipStream_t stream);
+// the same for P pulses: seg_prop (P,G,d,d) -> Qloc (P,G+1,d,d), totals (P,nchunks,d,d); restarts at every pulse
+hipError_t launch_scan_local_pulses(const cplx* seg_prop, int G, int P, int d, int L, cplx* Qloc,
+                                   cplx* totals, hipStream_t stream);
 // Q (G+1,d,d): Q[0] = 1, Q[g+1] = P[g] Q[g]
 hipError_t launch_prefix_products(const cplx* seg_prop, int G, int d, cplx* Q, void* ws,
                                   hipStream_t stream);
@@ -137,6 +150,14 @@ hipError_t launch_apply_prologue_compact(const cplx* Qloc, const cplx* totals, i
                                          const double* dt, const double* t, int A, double* segtab,
                                          cplx* Tc, cplx* ops, const cplx* basis, int N, void* ews,
                                          hipStream_t stream, cplx* wfold = nullptr);
+// The same for P pulses (every array pulse-major, t (P, G+1) pulse-local; n_opers (P,A,d,d), n_coeffs (P,A,G)):
+// block (segment, pulse); the basis is compacted once; wfold (P G A 64 for d = 4, P G A 512 for d = 8) or NULL.
+hipError_t launch_apply_prologue_compact_pulses(const cplx* Qloc, const cplx* totals, int G, int P, int d,
+                                                cplx* Q, const double* eigvals, const cplx* eigvecs,
+                                                const cplx* n_opers, const double* n_coeffs, const double* dt,
+                                                const double* t, int A, double* segtab, cplx* Tc, cplx* ops,
+                                                const cplx* basis, int N, void* ews, hipStream_t stream,
+                                                cplx* wfold = nullptr);
 // basis_transformed (G,N,d,d) = (Q^dag V)^dag C_k (Q^dag V)   (numeric.py:863-864)
 hipError_t launch_basis_transformed(const cplx* Tc, const cplx* basis, int G, int N, int d,
                                     cplx* out, hipStream_t stream);
@@ -163,6 +184,11 @@ struct AccumGeometry {
     bool d2 = false;  // folded-operand kernel for d = 2 (ctrl_d2.hip): independent wavefronts, one partial sum per block
 };
 void set_use_wave_kernel(bool on);
+// Geometry of P pulses of G segments run as ONE accumulate launch over the P G segments laid end to end: the chunk
+// length divides G, so every segment chunk (grid.z slab) lies inside one pulse and Ypart comes out pulse-major,
+// (P, chunks/P, A, d, d, W), with the instruction stream of the single-pulse kernels.  chunks/P is at most what
+// one pulse alone would get; usually 1 once P times the frequency tiles fill the device.
+AccumGeometry accumulate_geometry_pulses(int W, int A, int G, int d, int P);
 void set_use_gsplit(bool on);
 void set_mfma_policy(int policy);   // 0 default (d >= 12), 1 never, 2 wherever supported (d = 8 too)
 AccumGeometry accumulate_geometry(int W, int A, int G, int d, int forced_chunks);
@@ -275,6 +301,9 @@ hipError_t launch_expand_chunks(const cplx* Ypart, int chunks, size_t slab, int 
 bool expand_ff_supported(int A, int N);
 hipError_t launch_expand_ff(const cplx* Ypart, int chunks, size_t slab, int A, int N, int d, int W,
                             cplx* R, cplx* F, void* ws, hipStream_t stream);
+// ... for P pulses: block (frequency tile, pulse), pulse p sums Ypart[p chunks .. (p+1) chunks); R (P,A,N,W), F (P,A,A,W)
+hipError_t launch_expand_ff_pulses(const cplx* Ypart, int chunks, size_t slab, int A, int N, int d, int W,
+                                   int P, cplx* R, cplx* F, void* ws, hipStream_t stream);
 // `compacted`: the basis lists in ws were already produced by launch_reduce_and_compact
 hipError_t launch_expand(const cplx* Bt, const cplx* basis, int A2, int N, int d, int W, cplx* R,
                          void* ws, bool compacted, hipStream_t stream);
@@ -289,6 +318,10 @@ hipError_t launch_filter_function(const cplx* R, int A, int N, int W, int which,
 hipError_t launch_filter_function_weighted(const cplx* R, int A, int N, int W, const cplx* M,
                                            double scale, cplx* F, hipStream_t stream);
 size_t infidelity_workspace_bytes(int W, int n_idx, int s_ndim);
+// P filter functions (P, A, A, W) against one device-resident spectrum: infid (P, n_idx[, n_idx])
+hipError_t launch_infidelity_pulses(const cplx* F, int A, int W, int P, const cplx* S, int s_ndim,
+                                    const double* omega, const int32_t* idx, int n_idx, int d, double* infid,
+                                    hipStream_t stream);
 // spectrum_on_host: S (and idx) live in mapped pinned HOST memory: the spectrum is staged through LDS with all of
 // a thread's reads in flight at once (every read is a trip over PCIe); same sums in the same order.
 hipError_t launch_infidelity(const cplx* F, int A, int W, const cplx* S, int s_ndim,

@@ -519,16 +519,16 @@ __device__ __forceinline__ void infid_finish(double* red, const double (&acc)[kI
     }
 }
 
+// (output element p of one filter function; the kernels below pick p and the pulse)
 template <bool SHARDED>
-__global__ __launch_bounds__(kInfidThreads) void infid_kernel(const cplx* __restrict__ F, int A, int W,
-                                                              const cplx* __restrict__ S, int s_ndim,
-                                                              const double* __restrict__ omega,
-                                                              const int32_t* __restrict__ idx, int n_idx,
-                                                              int d, int shard_width,
-                                                              double* __restrict__ infid) {
+__device__ __forceinline__ void infid_element(const cplx* __restrict__ F, int A, int W,
+                                              const cplx* __restrict__ S, int s_ndim,
+                                              const double* __restrict__ omega,
+                                              const int32_t* __restrict__ idx, int n_idx,
+                                              int d, int shard_width,
+                                              double* __restrict__ infid, const int p) {
     __shared__ double red[kInfidSlots];
     __builtin_amdgcn_s_setprio(3);     // see ffk_internal.h FFK_SMALL_KERNEL_PRIORITY
-    const int p = blockIdx.x;  // output element
     int ia, ib;
     const cplx* Sp;
     if (s_ndim == 3) {
@@ -558,6 +558,26 @@ __global__ __launch_bounds__(kInfidThreads) void infid_kernel(const cplx* __rest
         asm volatile("" ::: "memory");      // (keeps the next batch's loads behind this batch's sums)
     }
     infid_finish<false>(red, acc, d, infid + p);
+}
+
+template <bool SHARDED>
+__global__ __launch_bounds__(kInfidThreads) void infid_kernel(const cplx* __restrict__ F, int A, int W,
+                                                              const cplx* __restrict__ S, int s_ndim,
+                                                              const double* __restrict__ omega,
+                                                              const int32_t* __restrict__ idx, int n_idx,
+                                                              int d, int shard_width,
+                                                              double* __restrict__ infid) {
+    infid_element<SHARDED>(F, A, W, S, s_ndim, omega, idx, n_idx, d, shard_width, infid, blockIdx.x);
+}
+
+// Batched form: block (output element, pulse) on the shared spectrum; F (P, A, A, W), infid (P, nout)
+__global__ __launch_bounds__(kInfidThreads) void infid_pulses_kernel(const cplx* __restrict__ F, int A, int W,
+                                                                     const cplx* __restrict__ S, int s_ndim,
+                                                                     const double* __restrict__ omega,
+                                                                     const int32_t* __restrict__ idx, int n_idx,
+                                                                     int d, int nout, double* __restrict__ infid) {
+    const size_t q = blockIdx.y;
+    infid_element<false>(F + q*A*A*W, A, W, S, s_ndim, omega, idx, n_idx, d, 0, infid + q*nout, blockIdx.x);
 }
 
 // The same integral with the spectrum in mapped pinned HOST memory (the resident API path hands it over
@@ -701,12 +721,11 @@ __global__ __launch_bounds__(64) void expand_chunks_kernel(const cplx* __restric
 // The same expansion followed, in the same launch, by the fidelity filter function of the block's
 // 16 frequencies: F[a,b,w] = sum_k conj(R[a,k,w]) R[b,k,w] (a <= b, mirrored; the summation order
 // of ff_fidelity_kernel).  Block = 16 frequencies x `kt` basis-element lanes; R passes through LDS.
-__global__ __launch_bounds__(256) void expand_ff_kernel(const cplx* __restrict__ Ypart, int chunks,
-                                                         size_t slab, const int* __restrict__ nnz,
-                                                         const int* __restrict__ rows,
-                                                         const cplx* __restrict__ vals, int N, int dd,
-                                                         int W, int A, int kt, cplx* __restrict__ R,
-                                                         cplx* __restrict__ F) {
+// (one pulse's partial sums; the kernels below pick the pulse)
+__device__ __forceinline__ void expand_ff_tile(const cplx* __restrict__ Ypart, int chunks, size_t slab,
+                                               const int* __restrict__ nnz, const int* __restrict__ rows,
+                                               const cplx* __restrict__ vals, int N, int dd, int W, int A,
+                                               int kt, cplx* __restrict__ R, cplx* __restrict__ F) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     cplx* rl = reinterpret_cast<cplx*>(lds_raw);       // [A][N][16]
     __builtin_amdgcn_s_setprio(3);     // see ffk_internal.h FFK_SMALL_KERNEL_PRIORITY
@@ -770,6 +789,28 @@ __global__ __launch_bounds__(256) void expand_ff_kernel(const cplx* __restrict__
     }
 }
 
+__global__ __launch_bounds__(256) void expand_ff_kernel(const cplx* __restrict__ Ypart, int chunks,
+                                                         size_t slab, const int* __restrict__ nnz,
+                                                         const int* __restrict__ rows,
+                                                         const cplx* __restrict__ vals, int N, int dd,
+                                                         int W, int A, int kt, cplx* __restrict__ R,
+                                                         cplx* __restrict__ F) {
+    expand_ff_tile(Ypart, chunks, slab, nnz, rows, vals, N, dd, W, A, kt, R, F);
+}
+
+// Batched form: block (frequency tile, pulse); pulse p reduces its own `chunks` partial sums
+// Ypart[p*chunks .. (p+1)*chunks) and writes R (P, A, N, W) and F (P, A, A, W).
+__global__ __launch_bounds__(256) void expand_ff_pulses_kernel(const cplx* __restrict__ Ypart, int chunks,
+                                                                size_t slab, const int* __restrict__ nnz,
+                                                                const int* __restrict__ rows,
+                                                                const cplx* __restrict__ vals, int N, int dd,
+                                                                int W, int A, int kt, cplx* __restrict__ R,
+                                                                cplx* __restrict__ F) {
+    const size_t p = blockIdx.y;
+    expand_ff_tile(Ypart + p*chunks*slab, chunks, slab, nnz, rows, vals, N, dd, W, A, kt,
+                   R + p*A*N*W, F + p*A*A*W);
+}
+
 bool expand_ff_supported(int A, int N) {
     // R tile [A][N][16] + summed partials [A][d^2][16], d^2 <= N for a complete basis; N bounds both
     return static_cast<size_t>(A)*2*N*16*sizeof(cplx) <= 128*1024;
@@ -794,6 +835,25 @@ hipError_t launch_expand_ff(const cplx* Ypart, int chunks, size_t slab, int A, i
         if (err != hipSuccess) return err;
     }
     hipLaunchKernelGGL(expand_ff_kernel, dim3((W + 15)/16), dim3(16*kt*at), lds, stream, Ypart,
+                       chunks, slab, cw.nnz, cw.rows, cw.vals, N, d*d, W, A, kt, R, F);
+    return hipGetLastError();
+}
+
+hipError_t launch_expand_ff_pulses(const cplx* Ypart, int chunks, size_t slab, int A, int N, int d, int W,
+                                   int P, cplx* R, cplx* F, void* ws, hipStream_t stream) {
+    if (!expand_ff_supported(A, N) || P < 1 || P > 65535) return hipErrorInvalidValue;
+    const CompactWs cw = slice_compact_ws(ws, N, d);
+    const int kt = N >= 16 ? 16 : (N >= 8 ? 8 : 4);
+    const int at = std::max(1, std::min(A, 16/kt));
+    const size_t lds = static_cast<size_t>(A)*(N + d*d)*16*sizeof(cplx);
+    if (lds > 160*1024) return hipErrorInvalidValue;
+    if (lds > 48*1024) {
+        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(expand_ff_pulses_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(lds));
+        if (err != hipSuccess) return err;
+    }
+    hipLaunchKernelGGL(expand_ff_pulses_kernel, dim3((W + 15)/16, P), dim3(16*kt*at), lds, stream, Ypart,
                        chunks, slab, cw.nnz, cw.rows, cw.vals, N, d*d, W, A, kt, R, F);
     return hipGetLastError();
 }
@@ -974,6 +1034,16 @@ size_t infidelity_workspace_bytes(int W, int n_idx, int s_ndim) {
     (void)n_idx;
     (void)s_ndim;
     return 256;  // none needed any more; kept non-zero so callers can always pass a buffer
+}
+
+hipError_t launch_infidelity_pulses(const cplx* F, int A, int W, int P, const cplx* S, int s_ndim,
+                                    const double* omega, const int32_t* idx, int n_idx, int d, double* infid,
+                                    hipStream_t stream) {
+    const int nout = s_ndim == 3 ? n_idx*n_idx : n_idx;
+    if (P < 1 || P > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(infid_pulses_kernel, dim3(nout, P), dim3(kInfidThreads), 0, stream, F, A, W, S, s_ndim,
+                       omega, idx, n_idx, d, nout, infid);
+    return hipGetLastError();
 }
 
 hipError_t launch_infidelity(const cplx* F, int A, int W, const cplx* S, int s_ndim,

@@ -178,20 +178,15 @@ inline bool split_noise_ops(int d, int A) { return d >= kNoiseOpsKernelMinD && A
 //   E_c = T_{c-1} ... T_0 rebuilt serially from the chunk totals (<= 63 small products, done
 //   redundantly by every block instead of a third launch), Q[g+1] = Qloc[g+1] E_c written out,
 //   Q[g] = Qloc[g] E_c kept in LDS and fed straight into the prologue.
+// (segment g of one pulse; the kernels below pick g and the pulse)
 template <int D>
-__global__ __launch_bounds__(64) void apply_prologue_kernel(
+__device__ __forceinline__ void apply_prologue_segment(
     const cplx* __restrict__ Qloc, const cplx* __restrict__ totals, int G, int L,
     cplx* __restrict__ Qout, const double* __restrict__ eigvals, const cplx* __restrict__ eigvecs,
     const cplx* __restrict__ n_opers, const double* __restrict__ n_coeffs,
     const double* __restrict__ dt, const double* __restrict__ t, int A,
     double* __restrict__ segtab, cplx* __restrict__ Tc, cplx* __restrict__ ops,
-    const cplx* __restrict__ basis, int* __restrict__ nnz, int* __restrict__ rows,
-    cplx* __restrict__ vals, bool with_noise_ops, cplx* __restrict__ wfold) {
-    // extra blocks (launch_apply_prologue_compact): basis compaction
-    if (static_cast<int>(blockIdx.x) >= G) {
-        basis_compact_one(basis, D, static_cast<int>(blockIdx.x) - G, threadIdx.x, nnz, rows, vals);
-        return;
-    }
+    bool with_noise_ops, cplx* __restrict__ wfold, const int g) {
     __builtin_amdgcn_s_setprio(3);     // see ffk_internal.h FFK_SMALL_KERNEL_PRIORITY
     __shared__ cplx E[2][D][D];
     __shared__ cplx M[D][D];
@@ -207,7 +202,6 @@ __global__ __launch_bounds__(64) void apply_prologue_kernel(
     // tools/corun.hip), else one batch
     extern __shared__ __attribute__((aligned(16))) unsigned char tot_raw[];
     cplx (*tot)[D][D] = reinterpret_cast<cplx (*)[D][D]>(tot_raw);
-    const int g = blockIdx.x;
     const int lane = threadIdx.x;
     const int c = g / L;
     for (int e = lane; e < D*D; e += 64) E[0][e / D][e % D] = {(e / D == e % D) ? 1.0 : 0.0, 0.0};
@@ -303,6 +297,48 @@ __global__ __launch_bounds__(64) void apply_prologue_kernel(
     __syncthreads();
     prologue_segment<D>(V, Q, T, BV, g, lane, eigvals, n_opers, n_coeffs, dt, t, G, A, segtab, Tc,
                         ops, nullptr, nullptr, with_noise_ops, wfold);
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void apply_prologue_kernel(
+    const cplx* __restrict__ Qloc, const cplx* __restrict__ totals, int G, int L,
+    cplx* __restrict__ Qout, const double* __restrict__ eigvals, const cplx* __restrict__ eigvecs,
+    const cplx* __restrict__ n_opers, const double* __restrict__ n_coeffs,
+    const double* __restrict__ dt, const double* __restrict__ t, int A,
+    double* __restrict__ segtab, cplx* __restrict__ Tc, cplx* __restrict__ ops,
+    const cplx* __restrict__ basis, int* __restrict__ nnz, int* __restrict__ rows,
+    cplx* __restrict__ vals, bool with_noise_ops, cplx* __restrict__ wfold) {
+    // extra blocks (launch_apply_prologue_compact): basis compaction
+    if (static_cast<int>(blockIdx.x) >= G) {
+        basis_compact_one(basis, D, static_cast<int>(blockIdx.x) - G, threadIdx.x, nnz, rows, vals);
+        return;
+    }
+    apply_prologue_segment<D>(Qloc, totals, G, L, Qout, eigvals, eigvecs, n_opers, n_coeffs, dt, t, A, segtab, Tc,
+                              ops, with_noise_ops, wfold, blockIdx.x);
+}
+
+// Batched form: block (segment, pulse) over P pulses of G segments, every array pulse-major (t pulse-local,
+// (P, G+1)); each block rebuilds the exclusive chunk prefix from its own pulse's totals.  The basis is compacted
+// once per pass, by the extra blocks of pulse 0.  The noise operators always ride in this kernel (no split).
+template <int D>
+__global__ __launch_bounds__(64) void apply_prologue_pulses_kernel(
+    const cplx* __restrict__ Qloc, const cplx* __restrict__ totals, int G, int L, int nchunks,
+    cplx* __restrict__ Qout, const double* __restrict__ eigvals, const cplx* __restrict__ eigvecs,
+    const cplx* __restrict__ n_opers, const double* __restrict__ n_coeffs,
+    const double* __restrict__ dt, const double* __restrict__ t, int A,
+    double* __restrict__ segtab, cplx* __restrict__ Tc, cplx* __restrict__ ops,
+    const cplx* __restrict__ basis, int* __restrict__ nnz, int* __restrict__ rows,
+    cplx* __restrict__ vals, cplx* __restrict__ wfold) {
+    const size_t p = blockIdx.y;
+    if (static_cast<int>(blockIdx.x) >= G) {
+        if (p == 0) basis_compact_one(basis, D, static_cast<int>(blockIdx.x) - G, threadIdx.x, nnz, rows, vals);
+        return;
+    }
+    constexpr size_t DD = D*D;
+    apply_prologue_segment<D>(Qloc + p*(G + 1)*DD, totals + p*nchunks*DD, G, L, Qout + p*(G + 1)*DD,
+                              eigvals + p*G*D, eigvecs + p*G*DD, n_opers + p*A*DD, n_coeffs + p*A*G, dt + p*G,
+                              t + p*(G + 1), A, segtab + p*G*seg_stride(D), Tc + p*G*DD, ops + p*G*(1 + A)*DD,
+                              true, wfold ? wfold + p*G*A*64 : nullptr, blockIdx.x);
 }
 
 // out[g,k] = T_g C_k T_g^dag with T_g = conj(Tc[g])   (= (Q^dag V)^dag C_k (Q^dag V))
@@ -458,6 +494,45 @@ hipError_t launch_apply_prologue_compact(const cplx* Qloc, const cplx* totals, i
             return hipErrorInvalidValue;
     }
     if (d == 8 && wfold != nullptr) return launch_fold_w8(segtab, ops, G, A, wfold, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_apply_prologue_compact_pulses(const cplx* Qloc, const cplx* totals, int G, int P, int d,
+                                                cplx* Q, const double* eigvals, const cplx* eigvecs,
+                                                const cplx* n_opers, const double* n_coeffs, const double* dt,
+                                                const double* t, int A, double* segtab, cplx* Tc, cplx* ops,
+                                                const cplx* basis, int N, void* ews, hipStream_t stream,
+                                                cplx* wfold) {
+    const int L = front_chunk(d);
+    const int nchunks = (G + L - 1)/L;
+    if (P < 1 || P > 65535 || !basis) return hipErrorInvalidValue;
+    int* nnz = nullptr;
+    int* rows = nullptr;
+    cplx* vals = nullptr;
+    expand_workspace_slices(ews, N, d, &nnz, &rows, &vals);
+    switch (d) {
+#define FFK_CASE(D)                                                                              \
+    case D:                                                                                      \
+        if (D > 8) {                                                                             \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(apply_prologue_pulses_kernel<D>), \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                                               static_cast<int>(sizeof(cplx)*D*D*16));           \
+            if (e != hipSuccess) return e;                                                       \
+        }                                                                                        \
+        hipLaunchKernelGGL(apply_prologue_pulses_kernel<D>, dim3(G + N, P), dim3(64),            \
+                           sizeof(cplx)*D*D*(D <= 8 ? nchunks : 16), stream, Qloc, totals, G, L, \
+                           nchunks, Q, eigvals, eigvecs, n_opers, n_coeffs, dt, t, A, segtab, Tc, \
+                           ops, basis, nnz, rows, vals, D == 4 ? wfold : nullptr);               \
+        break;
+        FFK_CASE(2) FFK_CASE(3) FFK_CASE(4) FFK_CASE(5) FFK_CASE(6) FFK_CASE(7) FFK_CASE(8)
+        FFK_CASE(9) FFK_CASE(10) FFK_CASE(11) FFK_CASE(12) FFK_CASE(13) FFK_CASE(14)
+        FFK_CASE(15) FFK_CASE(16)
+#undef FFK_CASE
+        default:
+            return hipErrorInvalidValue;
+    }
+    // (d = 8: the fold reads only segtab and ops, per segment: the P G segments in one launch)
+    if (d == 8 && wfold != nullptr) return launch_fold_w8(segtab, ops, P*G, A, wfold, stream);
     return hipGetLastError();
 }
 

@@ -36,15 +36,15 @@ __device__ __forceinline__ void matmul_lds(const cplx (*a)[D], const cplx (*b)[D
 // exposed memory round trip (~0.5 us) per segment.
 constexpr int kScanBatch = 16;   // propagators staged per batch
 
+// (chunk c of one pulse's G segments; the kernels below pick c and the pulse)
 template <int D>
-__global__ __launch_bounds__(64) void scan_local_kernel(const cplx* __restrict__ P, int G, int L,
-                                                        cplx* __restrict__ Q,
-                                                        cplx* __restrict__ totals) {
+__device__ __forceinline__ void scan_local_chunk(const cplx* __restrict__ P, int G, int L,
+                                                 cplx* __restrict__ Q, cplx* __restrict__ totals,
+                                                 const int c) {
     __shared__ cplx cur[2][D][D];
     __shared__ cplx pg[kScanBatch][D][D];
     __builtin_amdgcn_s_setprio(3);     // see ffk_internal.h FFK_SMALL_KERNEL_PRIORITY
     const int lane = threadIdx.x;
-    const int c = blockIdx.x;
     const int g0 = c*L, g1 = min(G, g0 + L);
     for (int e = lane; e < D*D; e += 64) cur[0][e / D][e % D] = {(e / D == e % D) ? 1.0 : 0.0, 0.0};
     if (c == 0)
@@ -127,6 +127,23 @@ __global__ __launch_bounds__(64) void scan_local_kernel(const cplx* __restrict__
         totals[static_cast<size_t>(c)*D*D + e] = cur[b][e / D][e % D];
 }
 
+template <int D>
+__global__ __launch_bounds__(64) void scan_local_kernel(const cplx* __restrict__ P, int G, int L,
+                                                        cplx* __restrict__ Q,
+                                                        cplx* __restrict__ totals) {
+    scan_local_chunk<D>(P, G, L, Q, totals, blockIdx.x);
+}
+
+// Batched form: block (chunk, pulse) over P pulses of G segments, pulse-major -- P (P, G, D, D), Q (P, G+1, D, D),
+// totals (P, nchunks, D, D).  A chunk never straddles two pulses: the scan restarts at every pulse.
+template <int D>
+__global__ __launch_bounds__(64) void scan_local_pulses_kernel(const cplx* __restrict__ P, int G, int L,
+                                                               cplx* __restrict__ Q,
+                                                               cplx* __restrict__ totals, int nchunks) {
+    const size_t p = blockIdx.y;
+    scan_local_chunk<D>(P + p*G*D*D, G, L, Q + p*(G + 1)*D*D, totals + p*nchunks*D*D, blockIdx.x);
+}
+
 // exclusive prefixes of the chunk totals, in place: totals[c] <- T_{c-1} ... T_0 (identity for c=0)
 template <int D>
 __global__ __launch_bounds__(64) void scan_totals_kernel(cplx* __restrict__ totals, int nchunks) {
@@ -194,6 +211,26 @@ hipError_t launch_scan_local(const cplx* seg_prop, int G, int d, int L, cplx* Ql
     case D:                                                                                      \
         hipLaunchKernelGGL(scan_local_kernel<D>, dim3(nchunks), dim3(64), 0, stream, seg_prop, G, \
                            L, Qloc, totals);                                                     \
+        break;
+        FFK_CASE(2) FFK_CASE(3) FFK_CASE(4) FFK_CASE(5) FFK_CASE(6) FFK_CASE(7) FFK_CASE(8)
+        FFK_CASE(9) FFK_CASE(10) FFK_CASE(11) FFK_CASE(12) FFK_CASE(13) FFK_CASE(14)
+        FFK_CASE(15) FFK_CASE(16)
+#undef FFK_CASE
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_local_pulses(const cplx* seg_prop, int G, int P, int d, int L, cplx* Qloc,
+                                   cplx* totals, hipStream_t stream) {
+    const int nchunks = (G + L - 1)/L;
+    if (P < 1 || P > 65535) return hipErrorInvalidValue;
+    switch (d) {
+#define FFK_CASE(D)                                                                                \
+    case D:                                                                                        \
+        hipLaunchKernelGGL(scan_local_pulses_kernel<D>, dim3(nchunks, P), dim3(64), 0, stream,     \
+                           seg_prop, G, L, Qloc, totals, nchunks);                                 \
         break;
         FFK_CASE(2) FFK_CASE(3) FFK_CASE(4) FFK_CASE(5) FFK_CASE(6) FFK_CASE(7) FFK_CASE(8)
         FFK_CASE(9) FFK_CASE(10) FFK_CASE(11) FFK_CASE(12) FFK_CASE(13) FFK_CASE(14)

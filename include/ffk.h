@@ -491,6 +491,30 @@ int ffk_pipeline_dev(const double* hamiltonian, const double* dt, const double* 
 int ffk_eigensolver_status_dev(const void* workspace, size_t workspace_bytes, int G, int d,
                                int32_t* n_failed, void* stream);
 
+/* ---- batched path: P pulses of one shape (d, G, n_cops, A, N) in ONE pass, the pulse a grid axis of every stage
+ *      (ff.get_filter_functions / ff.infidelities) -----------------------------------------------------------
+ * Per pulse, pulse-major: c_opers (P, n_cops, d, d) c128, c_coeffs (P, n_cops, G), dt (P, G), t (P, G+1) -- formed
+ * on the host per pulse exactly as for ffk_pipeline_dev --, n_opers (P, A, d, d), n_coeffs (P, A, G).  Shared by
+ * all pulses: omega (W,), basis (N, d, d), spectrum / s_ndim / idx as in ffk_pipeline_dev (may be NULL).  Outputs
+ * carry a leading P axis, any may be NULL: eigvals (P, G, d), eigvecs (P, G, d, d), propagators (P, G+1, d, d),
+ * control_matrix (P, A, N, W), filter_function (P, A, A, W), infid (P, n_idx[, n_idx]).  1 <= P <= 65535.
+ * Where the fused front applies (G <= 1024 for d <= 8, G <= 512 for d <= 16) and A N is small enough for the
+ * expansion kernel that also forms F (A (N + d^2) 256 B of LDS <= 128 KiB), each stage is one launch for all P
+ * pulses and the accumulate launch is the single-pulse kernel of the dimension over the P G segments laid end to
+ * end.  Every other shape with 2 <= d <= 16 runs P single passes of ffk_pipeline_dev on `stream` inside the call
+ * (same results; the integral is still one launch).                                                          */
+size_t ffk_pipeline_batch_workspace_bytes(int P, int W, int N, int A, int G, int d, int n_idx, int s_ndim);
+int ffk_pipeline_batch_dev(int P, const double* c_opers, int n_cops, const double* c_coeffs, const double* dt,
+                           const double* t, int G, int d, const double* omega, int W, const double* basis, int N,
+                           const double* n_opers, int A, const double* n_coeffs, const double* spectrum, int s_ndim,
+                           const int32_t* idx, int n_idx, double* eigvals, double* eigvecs, double* propagators,
+                           double* control_matrix, double* filter_function, double* infid, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* n_failed (P,) int32 on the device: flagged segments per pulse of the last ffk_pipeline_batch_dev run that used
+ * `workspace` (every word written).                                                                            */
+int ffk_eigensolver_status_batch_dev(const void* workspace, size_t workspace_bytes, int P, int G, int d,
+                                     int32_t* n_failed, void* stream);
+
 /* Fault word of the kernels whose wavefronts hand tiles to one another through flags in LDS (the d = 4
  * accumulation behind ffk_control_matrix*, ffk_pipeline_dev and the resident passes; reference loop
  * numeric.py:846-869).  Their waits are bounded; a wait that runs out stores a non-zero code in a word of mapped
@@ -563,6 +587,22 @@ int ffk_resident_control_matrix_dev(ffk_resident* handle, const double** control
 int ffk_resident_infidelity(ffk_resident* handle, const double* spectrum, int s_ndim,
                             int spectrum_is_real, const int32_t* idx, int n_idx, int d,
                             double* infid);
+/* The batch counterpart of ffk_resident_filter_function_infidelity: P pulses (arrays as for ffk_pipeline_batch_dev,
+ * host pointers) staged with ONE H2D copy, one batched pass, ONE D2H copy of eigvals (P, G, d), eigvecs, propagators
+ * and filter_function (P, A, A, W) into the handle's pinned block.  spectrum may be NULL (no integral); else it is
+ * shared by all pulses as in ffk_resident_filter_function_infidelity and infidelity is (P, n_idx[, n_idx]).
+ * n_failed (P,) int32 host: flagged segments per pulse; any non-zero entry returns FFK_ENOCONV naming the first such
+ * pulse, and the results are then not valid.  The control matrices (P, A, N, W) stay in HBM:
+ * ffk_resident_batch_control_matrix copies pulse `pulse`'s (A, N, W) out.                                      */
+int ffk_resident_batch_filter_function_infidelity(ffk_resident* handle, int P, const double* c_opers, int n_cops,
+                                                  const double* c_coeffs, const double* dt, const double* t, int G,
+                                                  int d, const double* omega, int W, const double* basis, int N,
+                                                  const double* n_opers, int A, const double* n_coeffs,
+                                                  const double* spectrum, int s_ndim, int spectrum_is_real,
+                                                  const int32_t* idx, int n_idx, int d_infidelity, double** eigvals,
+                                                  double** eigvecs, double** propagators, double** filter_function,
+                                                  double* infidelity, int32_t* n_failed);
+int ffk_resident_batch_control_matrix(ffk_resident* handle, int pulse, double* control_matrix);
 
 /* ---- one-sided all-gather of the F blocks over xGMI (frequency-sharded step; the
  *      reference has no multi-device path: numeric.py:846-869 is embarrassingly parallel in omega

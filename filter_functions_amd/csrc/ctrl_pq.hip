@@ -36,7 +36,9 @@
 //     serves A operators as groups of three plus groups of two (A = 4: 2 + 2, 5: 3 + 2, 7: 3 + 2 + 2) instead of
 //     a zero-padded three-operator block (profiles/r06_*).
 //   * W_a comes folded from the prologue kernel where the caller owns a buffer for it (PRE: wfold != nullptr,
-//     ffk_control_matrix_dev / ffk_pipeline_dev), else the producers fold it per tile.
+//     ffk_control_matrix_dev / ffk_pipeline_dev), else the producers fold it per tile.  Round 7: with PRE, W_a and
+//     T go from global memory into the slot by LDS-DMA, and the consumer loop issues all its LDS operations in
+//     the gaps behind its matrix instructions (profiles/r07_*).
 //   * Flags in LDS: ready[slot] written by the slot's producer, done[slot] counted up by the consumers with
 //     ds_add, progress[consumer]; the lagging consumer of a SIMD raises its priority (the arbiter serves the
 //     oldest wavefront first and would let one run ahead until the ring stops it: soft lockstep).  Every wait is
@@ -52,6 +54,7 @@
 #include <cstdlib>
 
 #include "ffk_internal.h"
+#include "ffk_mfma_util.h"
 
 namespace ffk {
 namespace {
@@ -142,22 +145,48 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
         // consumers want one per 1430, and a starved ring costs more than it saves.  profiles/r05_l_*.)
         __builtin_amdgcn_s_setprio(0);
         const int iw = blockIdx.x*64 + lane;
-        const double om = omega[iw < W ? iw : W - 1];
+        double om = omega[iw < W ? iw : W - 1];
+        // (landed here, once: the loop's own counted waits below do not cover it, and hipcc would otherwise drain every
+        // load in flight, the next row's included, in front of its first use inside the loop)
+        asm volatile("" : "+v"(om));
         const int n_ops = (1 + n_alpha)*DD;            // <= 64: one staged element per lane
         double* row = rows + wave*S;
         struct Staged {
             cplx o;            // lane l: element l of [T | Bbar_0 | Bbar_1 ..] of the segment
             double r0, r1;     // doubles l and (l < 8) 64 + l of the table row
         };
+        // (PRE: T and W_a go to the slot by LDS-DMA, o is not needed; the row's two loads are unconditional, a
+        // fixed count of vector-memory instructions behind the copies: the counted wait below relies on it)
         auto request = [&](int it) __attribute__((always_inline)) -> Staged {
             const int g = g0 + it;
             const cplx* src = ops + static_cast<size_t>(g)*(1 + A)*DD;
             const double* st = segtab + static_cast<size_t>(g)*S;
             Staged t;
-            t.o = lane < n_ops ? src[lane < DD ? lane : lane + alpha0*DD] : cplx{0.0, 0.0};
-            t.r0 = st[lane];
-            t.r1 = lane < S - 64 ? st[64 + lane] : 0.0;
+            if constexpr (PRE) {
+                t.o = cplx{0.0, 0.0};
+                t.r0 = st[lane];
+                t.r1 = st[64 + (lane & (S - 64 - 1))];
+            } else {
+                t.o = lane < n_ops ? src[lane < DD ? lane : lane + alpha0*DD] : cplx{0.0, 0.0};
+                t.r0 = st[lane];
+                t.r1 = lane < S - 64 ? st[64 + lane] : 0.0;
+            }
             return t;
+        };
+        // the slot's previous tenant (tile it - 8) has been read by every consumer?
+        auto wait_slot = [&](int slot, int gen) __attribute__((always_inline)) {
+            if (gen > 0) {
+                int spin = 0;
+                for (; spin < spin_limit; ++spin) {
+                    if (lds_peek(done + slot) >= gen*kPqConsumers) break;
+                    __builtin_amdgcn_s_sleep(2);
+                }
+                if (spin == spin_limit && spin_limit != 0) {
+                    pq_report_fault(fault_word, kFaultPcProducerWait);
+                    spin_limit = 0;
+                }
+                asm volatile("" ::: "memory");
+            }
         };
         Staged cur = {};
         if (wave < n_it) cur = request(wave);
@@ -168,6 +197,19 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
             row[lane] = cur.r0;
             if (lane < S - 64) row[64 + lane] = cur.r1;
             const cplx o = cur.o;
+            if constexpr (PRE) {
+                // The slot first (the producers wait for it 560-1000 cycles per tile anyway),
+                // then the pre-folded W_a of the segment (1 KiB per operator, in the consumers' order) and T (256 B)
+                // copied into it by LDS-DMA: no registers, no ds_write_b128 (a 16-byte store costs a wavefront 34-44
+                // cycles beside matrix instructions, profiles/r06_b_*).  The copies are issued BEFORE the next
+                // tile's row is requested, so that their wait below does not drain that request.
+                wait_slot(slot, gen);
+                const size_t gw = (static_cast<size_t>(g0 + it)*A + alpha0)*64;
+#pragma unroll
+                for (int a = 0; a < NC; ++a)
+                    if (a < n_alpha) lds_dma16(wfold + gw + a*64 + lane, buf + kPqW + a*128);
+                if (lane < DD) lds_dma16(ops + static_cast<size_t>(g0 + it)*(1 + A)*DD + lane, buf + TOP);
+            }
             if (it + kPqProducers < n_it) cur = request(it + kPqProducers);
             // The records of the row are requested in two batches, each all at once (the compiler otherwise
             // fetches them in pairs with a full LDS round trip between the pairs; all 13 at once take 104 registers).
@@ -215,28 +257,7 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
             q[5] = q[0];
             q[10] = q[0];
             q[15] = q[0];
-            // the pre-folded W_a of the segment (element `lane` of each operator's 64): requested HERE, with the tile's
-            // records dead, and used behind the wait for the slot -- staged a tile ahead like the row it cost 12
-            // registers across the whole tile: 168 with spills where the consumers' loop needs 146
-            cplx wpre[NC];
-            if constexpr (PRE) {
-#pragma unroll
-                for (int a = 0; a < NC; ++a)
-                    wpre[a] = a < n_alpha ? wfold[(static_cast<size_t>(g0 + it)*A + alpha0 + a)*64 + lane] : cplx{0.0, 0.0};
-            }
-            // the slot's previous tenant (tile it - 8) has been read by every consumer?
-            if (gen > 0) {
-                int spin = 0;
-                for (; spin < spin_limit; ++spin) {
-                    if (lds_peek(done + slot) >= gen*kPqConsumers) break;
-                    __builtin_amdgcn_s_sleep(2);
-                }
-                if (spin == spin_limit && spin_limit != 0) {
-                    pq_report_fault(fault_word, kFaultPcProducerWait);
-                    spin_limit = 0;
-                }
-                asm volatile("" ::: "memory");
-            }
+            if constexpr (!PRE) wait_slot(slot, gen);
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -249,14 +270,8 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
                 *reinterpret_cast<double2_t*>(buf + kPqPsi + lane*2) = v;
             }
             // W_a[m][n][j] = Bbar_a[m][n] e^{i b_mn} T[n][j], (m, n, j) = this lane's index: folded once per segment
-            // by the prologue kernel where the caller gave it a buffer (wfold), else here
-            if constexpr (PRE) {
-#pragma unroll
-                for (int a = 0; a < NC; ++a) {
-                    const double2_t v = {wpre[a].re, wpre[a].im};
-                    *reinterpret_cast<double2_t*>(buf + kPqW + a*128 + lane*2) = v;
-                }
-            } else {
+            // by the prologue kernel where the caller gave it a buffer (wfold, copied in above), else here
+            if constexpr (!PRE) {
                 const int src_t = lane & (DD - 1);                          // T[n][j]
                 const cplx tv = {__shfl(o.re, src_t, 64), __shfl(o.im, src_t, 64)};
                 const cplx et = cmul(cplx{cb, sb}, tv);
@@ -270,7 +285,12 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
                     *reinterpret_cast<double2_t*>(buf + kPqW + a*128 + wslot*2) = v;
                 }
             }
-            if (lane < DD) {
+            if constexpr (PRE) {
+                // the copies landed: every vector-memory operation but the next row's two loads, issued behind them
+                // (none behind the producer's last tile)
+                if (it + kPqProducers < n_it) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                else lds_dma_wait();
+            } else if (lane < DD) {
                 const double2_t v = {o.re, o.im};
                 *reinterpret_cast<double2_t*>(buf + TOP + lane*2) = v;
             }

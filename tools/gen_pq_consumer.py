@@ -35,8 +35,17 @@ Registers of the NC-operator block (fixed; `{v[a:b]}` constraints in the generat
     loop registers (LDS addresses of both ring halves, flags, counters)                   18
 i.e. 142 / 108 / 74 for NC = 3 / 2 / 1.  Scalars: inputs s[36:39] = (tiles, spin limit, LDS address of the
 flags, consumer number), output s48 = 0 or the fault code of a flag wait that ran out; s[40:51] scratch.
-LDS operations of a tile, in queue order: flag of tile it + 2, partner's progress | set 1's psi, q01, q23 |
-next tile's W[.][0], T, psi, q01, W[.][1], W[.][2], q23, W[.][3] | done counter, own progress.
+LDS operations of a tile, in queue order (round 7: every one of them in a gap behind a matrix instruction, none
+between the vector instructions of a set):
+    in set 0's matrix instructions   set 1's psi, q01 | flag of tile it + 2, partner's progress | set 1's q23 |
+                                     done counter, own progress
+    in set 1's matrix instructions   next tile's T, psi, q01, W[.][0], W[.][1], W[.][2], q23, W[.][3]
+Set 0's q01, q23, psi are dead during its matrix instructions (set 1 reads its own there); during set 1's matrix
+instructions every operand register is dead.  The reads are dealt out evenly, the earlier gaps taking the extra
+one (the first-needed operands arrive first): 7 in 9 and 16 in 9 gaps for NC = 3, 7 in 6 and 12 in 6 for NC = 2,
+7 in 3 and 8 in 3 for NC = 1.  The done counter follows the slot's last read (set 1's q23) in the in-order queue;
+the own progress (tiles finished before this one) is published with it, half a tile later than the end of the
+tile that it counts.
 """
 RING = 8
 SETS = 2                # sets of four frequencies per consumer
@@ -76,7 +85,7 @@ class Map:
         self.t_off = nc*W_BYTES                       # (tr, ti) pairs behind the operators' W, same lane index
         self.tile_bytes = (1152 + nc*128 + 32)*8      # ctrl_pq.hip: pq_tile_doubles(NC) * 8 (checked there)
         # the LDS queue at the top of a tile: what the previous tile left in flight
-        self.entry = ['w0']*nc + ['T', 'psi', 'q01'] + ['w1']*nc + ['w2']*nc + ['q23'] + ['w3']*nc + ['done', 'prog']
+        self.entry = ['done', 'prog', 'T', 'psi', 'q01'] + ['w0']*nc + ['w1']*nc + ['w2']*nc + ['q23'] + ['w3']*nc
 
     def wre(self, a, n):
         return self.w0 + 4*(4*a + n)
@@ -110,28 +119,24 @@ class Stream:
             self.fifo = self.fifo[len(self.fifo) - 15:]
 
 
-def next_tile_requests(st, M, adr, stage):
-    """The next tile's operands, each requested right behind the LAST use of the registers it lands in (the last
-    set's vector stages): W[.][n] is dead after stage n + 1, T, psi and q01 after stage 2, q23 after stage 4.
-    (All of them in one burst behind stage 4 cost 3.7 us of the consumers' 54.7: profiles/r05_b_*.)"""
+def next_tile_requests(M, adr):
+    """The next tile's operands as LDS items, in the order of their first use: dealt into the gaps of the last set's
+    matrix instructions, when every operand register is dead.  (Round 6: each behind the last vector instruction
+    that read its registers, in bursts of 3-6 between the vector instructions; round 5: all in one burst behind
+    stage 4, 3.7 us of the consumers' 54.7, profiles/r05_b_*.)"""
+    items = [[(f'ds_read_b128 {v4(M.t)}, {adr("a_w", M.t_off)}', 'T')],
+             [(f'ds_read_b128 {v4(M.psi)}, {adr("a_p")}', 'psi')],
+             [(f'ds_read_b128 {v4(M.q01)}, {adr("a_q0")}', 'q01')]]
+
     def w(n):
-        for a in range(M.nc):
-            st.lds(f'ds_read_b128 {v4(M.wre(a, n))}, {adr("a_w", a*W_BYTES + n*256)}', f'w{n}')
-    if stage == 1:
-        w(0)
-    elif stage == 2:
-        st.lds(f'ds_read_b128 {v4(M.t)}, {adr("a_w", M.t_off)}', 'T')
-        st.lds(f'ds_read_b128 {v4(M.psi)}, {adr("a_p")}', 'psi')
-        st.lds(f'ds_read_b128 {v4(M.q01)}, {adr("a_q0")}', 'q01')
-        w(1)
-    elif stage == 3:
-        w(2)
-    elif stage == 4:
-        st.lds(f'ds_read_b128 {v4(M.q23)}, {adr("a_q0", 4096)}', 'q23')
-        w(3)
+        return [[(f'ds_read_b128 {v4(M.wre(a, n))}, {adr("a_w", a*W_BYTES + n*256)}', f'w{n}')] for a in range(M.nc)]
+    items += w(0) + w(1) + w(2)
+    items.append([(f'ds_read_b128 {v4(M.q23)}, {adr("a_q0", 4096)}', 'q23')])
+    items += w(3)
+    return items
 
 
-def vector_part(st, M, after_stage):
+def vector_part(st, M):
     q = [M.q01, M.q01 + 2, M.q23, M.q23 + 2]
     pr, pi = M.psi, M.psi + 2
     tr, ti = M.t, M.t + 2
@@ -142,7 +147,6 @@ def vector_part(st, M, after_stage):
     for a in range(M.nc):
         st.emit(f'v_mul_f64 {v(M.zr[a])}, {v(q[0])}, {v(M.wre(a, 0))}')
         st.emit(f'v_mul_f64 {v(M.zi[a])}, {v(q[0])}, {v(M.wre(a, 0) + 2)}')
-    after_stage(1)
     # stage 2
     st.need('w1')
     st.emit(f'v_fma_f64 {v(M.cr)}, {v(pr)}, {v(tr)}, {v(M.cr)}')
@@ -150,38 +154,54 @@ def vector_part(st, M, after_stage):
     for a in range(M.nc):
         st.emit(f'v_fma_f64 {v(M.zr[a])}, {v(q[1])}, {v(M.wre(a, 1))}, {v(M.zr[a])}')
         st.emit(f'v_fma_f64 {v(M.zi[a])}, {v(q[1])}, {v(M.wre(a, 1) + 2)}, {v(M.zi[a])}')
-    after_stage(2)
     # stage 3
     st.need('q23', 'w2')
     st.emit(f'v_add_f64 {v(M.cs)}, {v(M.cr)}, {v(M.ci)}')
     for a in range(M.nc):
         st.emit(f'v_fma_f64 {v(M.zr[a])}, {v(q[2])}, {v(M.wre(a, 2))}, {v(M.zr[a])}')
         st.emit(f'v_fma_f64 {v(M.zi[a])}, {v(q[2])}, {v(M.wre(a, 2) + 2)}, {v(M.zi[a])}')
-    after_stage(3)
     # stage 4
     st.need('w3')
     for a in range(M.nc):
         st.emit(f'v_fma_f64 {v(M.zr[a])}, {v(q[3])}, {v(M.wre(a, 3))}, {v(M.zr[a])}')
         st.emit(f'v_fma_f64 {v(M.zi[a])}, {v(q[3])}, {v(M.wre(a, 3) + 2)}, {v(M.zi[a])}')
-    after_stage(4)
 
 
-def matrix_part(st, M, s, glue):
-    """the 3 NC matrix instructions of a set; `glue`: scalar / address instructions of the loop, dealt out behind
-    the matrix instructions"""
+def split(n, parts, front=True):
+    """n items over `parts` gaps as evenly as possible, the extra ones in the first (front) or last gaps"""
+    base, extra = divmod(n, parts)
+    sizes = [base + (k < extra) for k in range(parts)]
+    return sizes if front else sizes[::-1]
+
+
+def matrix_part(st, M, s, lds_items, glue):
+    """The 3 NC matrix instructions of a set with the LDS items and the loop's scalar / address instructions (`glue`)
+    dealt out into the gaps behind them: a gap takes its LDS operations first, the LDS items are spread evenly with
+    the extra ones in the first gaps, the glue with the extra ones in the last.  An item is a list of lines, an LDS
+    line a (text, tag) pair; a str glue item is one line, a tuple lines kept together (branches among them).
+    Behind a matrix instruction a ds_read_b128 every second gap costs the wavefront 0.5 cycles, one per gap 4, a burst
+    up to 7.3 (profiles/r06_b_*)."""
     for a in range(M.nc):
         st.emit(f'v_add_f64 {v(M.zs[a])}, {v(M.zr[a])}, {v(M.zi[a])}')
-    glue = list(glue)
-    per = -(-len(glue)//(3*M.nc)) if glue else 0
+    gaps = 3*M.nc
+    lds_items, glue = list(lds_items), list(glue)
+    n_lds, n_glue = split(len(lds_items), gaps), split(len(glue), gaps, front=False)
+    g = 0
     for a in range(M.nc):
         for k, (src_a, src_b) in enumerate(((M.cr, M.zr[a]), (M.ci, M.zi[a]), (M.cs, M.zs[a]))):
             st.emit(f'v_mfma_f64_4x4x4_4b_f64 {v(M.acc(a, s, k))}, {v(src_a)}, {v(src_b)}, {v(M.acc(a, s, k))}')
-            for _ in range(per):
-                if glue:
-                    item = glue.pop(0)          # a tuple: instructions with branches among them, kept together
-                    for line in ((item,) if isinstance(item, str) else item):
+            for _ in range(n_lds[g]):
+                for line in lds_items.pop(0):
+                    if isinstance(line, tuple):
+                        st.lds(*line)
+                    else:
                         st.emit(line)
-    assert not glue
+            for _ in range(n_glue[g]):
+                item = glue.pop(0)
+                for line in ((item,) if isinstance(item, str) else item):
+                    st.emit(line)
+            g += 1
+    assert not lds_items and not glue
 
 
 def priority_rule(M, k):
@@ -241,18 +261,19 @@ def build_loop(M):
             assert 0 <= off < 65536
             return f'{regs[name]} offset:{off}' if off else regs[name]
 
-        st.lds(f'ds_read_b32 {V["flag"]}, {v_flags} offset:{4*((k + 2) % RING)}', 'flag')
-        st.lds(f'ds_read_b32 {V["partner"]}, {V["a_partner"]} offset:64', 'partner')
-
-        def second_set(stage):
-            # set 1's psi, q01 behind stage 2 (their registers' last use), q23 behind stage 4: they arrive during
-            # the rest of the set and its matrix instructions
-            if stage == 2:
-                st.lds(f'ds_read_b128 {v4(M.psi)}, {adr("a_p1", 64)}', 'psi')
-                st.lds(f'ds_read_b128 {v4(M.q01)}, {adr("a_q1")}', 'q01')
-            elif stage == 4:
-                st.lds(f'ds_read_b128 {v4(M.q23)}, {adr("a_q1", 4096)}', 'q23')
-        vector_part(st, M, second_set)
+        vector_part(st, M)
+        # set 1's psi, q01, q23 (set 0 is done with its own), the flag of tile it + 2 and the partner's progress (read a
+        # tile ahead), then -- behind the slot's last read -- the slot handed back: lane 0 counts this consumer in and
+        # publishes its progress (LDS operations of a wavefront execute in order: no wait)
+        set1 = [[(f'ds_read_b128 {v4(M.psi)}, {adr("a_p1", 64)}', 'psi')],
+                [(f'ds_read_b128 {v4(M.q01)}, {adr("a_q1")}', 'q01')],
+                [(f'ds_read_b32 {V["flag"]}, {v_flags} offset:{4*((k + 2) % RING)}', 'flag')],
+                [(f'ds_read_b32 {V["partner"]}, {V["a_partner"]} offset:64', 'partner')],
+                [(f'ds_read_b128 {v4(M.q23)}, {adr("a_q1", 4096)}', 'q23')],
+                ['s_mov_b64 exec, 1', (f'ds_add_u32 {v_flags}, {V["one"]} offset:{4*RING + 4*k}', 'done'),
+                 's_mov_b64 exec, -1'],
+                ['s_mov_b64 exec, 1', (f'ds_write_b32 {V["a_prog"]}, {V["progress"]} offset:64', 'prog'),
+                 's_mov_b64 exec, -1']]
         # tile it + 1 published?  (its flag was read a tile ago; the slow path spins, bounded; no wait behind the last tile)
         glue0 = [f's_add_i32 {S["t"]}, {S["it"]}, 2',
                  (f's_cmp_ge_i32 {S["fnext"]}, {S["t"]}',
@@ -262,19 +283,15 @@ def build_loop(M):
                   f's_cbranch_scc1 L_ready{k}_%=',
                   f's_branch L_spin{k}_%=',
                   f'L_ready{k}_%=:')]
-        matrix_part(st, M, 0, glue0)
+        matrix_part(st, M, 0, set1, glue0)
         # T and W are still this tile's: only q01, q23, psi have to arrive
-        st.fifo = [t if t in ('q01', 'q23', 'psi', 'flag', 'partner') else 'old' for t in st.fifo]
-        vector_part(st, M, lambda stage: next_tile_requests(st, M, adr, stage))
+        st.fifo = [t if t in ('q01', 'q23', 'psi', 'flag', 'partner', 'done', 'prog') else 'old' for t in st.fifo]
+        vector_part(st, M)
+        # (the flag and the partner's progress were queued ahead of set 1's q23: its wait covered them)
+        assert 'flag' not in st.fifo and 'partner' not in st.fifo, st.fifo
         glue1 = [f'v_readfirstlane_b32 {S["fnext"]}, {V["flag"]}',
                  f'v_add_u32_e32 {V["progress"]}, 1, {V["progress"]}'] + priority_rule(M, k)
-        matrix_part(st, M, 1, glue1)
-        # hand the slot back: lane 0 counts this consumer in and publishes its progress (LDS operations of a
-        # wavefront execute in order: both are behind the tile's reads without a wait)
-        e('s_mov_b64 exec, 1')
-        st.lds(f'ds_add_u32 {v_flags}, {V["one"]} offset:{4*RING + 4*k}', 'done')
-        st.lds(f'ds_write_b32 {V["a_prog"]}, {V["progress"]} offset:64', 'prog')
-        e('s_mov_b64 exec, -1')
+        matrix_part(st, M, 1, next_tile_requests(M, adr), glue1)
         assert st.fifo == M.entry, st.fifo
         e(f's_add_i32 {S["it"]}, {S["it"]}, 1')
         e(f's_cmp_ge_i32 {S["it"]}, {S["nit"]}')
@@ -318,8 +335,9 @@ def prologue(M):
 
     def adr(name, offset=0):
         return f'%[{name}] offset:{offset}' if offset else f'%[{name}]'
-    for stage in (1, 2, 3, 4):
-        next_tile_requests(st, M, adr, stage)
+    for item in next_tile_requests(M, adr):
+        for line in item:
+            st.lds(*line)
     st.emit('s_waitcnt lgkmcnt(0)')
     return st
 

@@ -13,20 +13,22 @@ The arithmetic runs in hand-written HIP kernels for gfx950 behind a C ABI
 side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
-from . import analytic, basis, batch, gradient, numeric, pulse_sequence, superoperator, util
+from . import analytic, basis, batch, gradient, numeric, pulse_sequence, sequences, superoperator, util
 from .basis import Basis
 from .batch import get_filter_functions, infidelities
 from .gradient import infidelity_derivative
 from .numeric import error_transfer_matrix, infidelity
+from .sequences import concatenate_sequences
 from .pulse_sequence import (PulseSequence, concatenate, concatenate_periodic,
                              concatenate_without_filter_function, extend, remap)
 from .superoperator import liouville_representation
 
 __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'concatenate', 'concatenate_periodic',
+           'concatenate_sequences',
            'concatenate_without_filter_function',
            'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
            'infidelity_derivative',
            'liouville_representation', 'numeric',
-           'pulse_sequence', 'remap', 'superoperator', 'util']
+           'pulse_sequence', 'remap', 'sequences', 'superoperator', 'util']
 
 __version__ = '0.1.0'

@@ -238,6 +238,14 @@ SIGNATURES = {
                                                               POINTER(c_void_p), POINTER(c_void_p),
                                                               POINTER(c_void_p), c_void_p, c_void_p]),
     'ffk_resident_batch_control_matrix': (c_int, [c_void_p, c_int, c_void_p]),
+    'ffk_concatenate_sequences_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                             c_int, c_int]),
+    'ffk_concatenate_sequences_resident': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                   c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                                   c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                                   c_void_p, c_void_p, c_void_p]),
+    'ffk_resident_batch_infidelity': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                              c_int, c_void_p]),
     'ffk_ipc_get_handle': (c_int, [c_void_p, c_void_p]),
     'ffk_ipc_open_handle': (c_int, [c_void_p, POINTER(c_void_p)]),
     'ffk_ipc_close_handle': (c_int, [c_void_p]),

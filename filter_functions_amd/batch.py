@@ -97,13 +97,14 @@ class BatchResult:
 class _Member:
     """``pulse._resident`` of a batch member: keeps the batch alive, but is no single-pulse resident
     result (no ``shape``, no resident filter function), so the integral of a later ``ff.infidelity`` and
-    ``concatenate`` take their array routes.  Copies of the pulse drop it, as they drop a resident result."""
-    __slots__ = ('batch',)
+    ``concatenate`` take their array routes (``ff.concatenate_sequences`` reads member ``slot`` in place).  Copies
+    of the pulse drop it, as they drop a resident result."""
+    __slots__ = ('batch', 'slot')
     shape = None
     filter_function = None
 
-    def __init__(self, batch):
-        self.batch = batch
+    def __init__(self, batch, slot=None):
+        self.batch, self.slot = batch, slot      # (slot: the pulse's index in the pass)
 
     def __deepcopy__(self, memo):
         return None
@@ -174,15 +175,37 @@ def _run_pass(pulses, members, omega, basis, spectrum=None, idx=None):
         raise np.linalg.LinAlgError(f'Eigensolver did not converge for pulse {failed[0]} of the list '
                                     f'({int(err.n_failed[members.index(failed[0])])} segment(s)); '
                                     f'pulses that failed: {failed}') from err
-    member = _Member(batch)
     nbytes = 16*F.shape[1]*len(basis)*F.shape[3]
     for j, pulse in enumerate(group):
         pulse._data.update(eigvals=D[j], eigvecs=V[j], propagators=Q[j], total_propagator=Q[j][-1])
         pulse._frequency_data['control_matrix'] = Deferred(functools.partial(batch.control_matrix, j), nbytes)
         pulse._frequency_data['filter_function'] = F[j]
         pulse._defer_by_products()
-        pulse._resident = member
+        pulse._resident = _Member(batch, j)
     return F, infid
+
+
+def _sequence_pass_integrals(pulses, spectrum, omega, idx_of, eligible, out):
+    """The infidelities of results of ``ff.concatenate_sequences`` whose resident filter function ``ff.infidelity``
+    would integrate in place: the members of one pass (same selected operators and dimension) in ONE launch."""
+    from .sequences import _SequenceMember
+    skip = set(eligible)
+    groups = {}
+    for i, pulse in enumerate(pulses):
+        member = pulse._resident
+        if i in skip or not isinstance(member, _SequenceMember) or not pulse.basis.istraceless:
+            continue
+        # (what ff.infidelity reads before it asks pulse.resident_infidelity)
+        if pulse.get_filter_function(omega, which='fidelity') is not member.filter_function \
+                or pulse._resident is not member:
+            continue
+        key = (id(member.batch), tuple(int(k) for k in idx_of[i]), pulse.d)
+        groups.setdefault(key, (member.batch, []))[1].append(i)
+    for (_, idx, d), (batch, members) in groups.items():
+        parsed = util.parse_spectrum(spectrum, as_f64(omega), np.asarray(idx))
+        values = batch.infidelities([pulses[i]._resident.slot for i in members], parsed, idx, d)
+        for i, value in zip(members, values):
+            out[i] = value
 
 
 def _results(pulses, omega, spectrum, n_oper_identifiers):
@@ -198,6 +221,8 @@ def _results(pulses, omega, spectrum, n_oper_identifiers):
     eligible = [i for i, p in enumerate(pulses)
                 if p.nothing_cached_for(omega) and (not with_integral or p.basis.istraceless)]
     out = [None]*len(pulses)
+    if with_integral:
+        _sequence_pass_integrals(pulses, spectrum, omega, idx_of, eligible, out)
     whole = None          # F of a single pass that covers the whole list in input order: returned as it is
     for members in group_pulses(pulses, eligible, idx_of):
         first = pulses[members[0]]

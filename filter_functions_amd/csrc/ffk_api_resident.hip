@@ -126,6 +126,8 @@ struct ffk_resident {
     int P = 0;
     bool batch_valid = false;
     size_t batch_R = 0;           // device offset of the control matrices (P, A, N, W)
+    size_t batch_F = 0;           // device offsets of the filter functions (P, A, A, W) and of the grid (W)
+    size_t batch_omega = 0;
 };
 
 extern "C" {
@@ -688,7 +690,8 @@ int ffk_resident_batch_filter_function_infidelity(ffk_resident* r, int P, const 
         if (int rc = g_pin_pool.take(outputs_end, dev, &r->pin)) return rc;
         r->device = dev;
     }
-    r->P = P; r->G = G; r->d = d; r->W = W; r->N = N; r->A = A; r->batch_R = o_R;
+    r->P = P; r->G = G; r->d = d; r->W = W; r->N = N; r->A = A; r->batch_R = o_R; r->batch_F = o_F;
+    r->batch_omega = o_om;
     unsigned char* hp = static_cast<unsigned char*>(r->pin.ptr);
     unsigned char* dp = static_cast<unsigned char*>(r->dev.ptr);
     const auto clock0 = std::chrono::steady_clock::now();
@@ -831,6 +834,279 @@ int ffk_resident_infidelity(ffk_resident* r, const double* spectrum, int s_ndim,
         }
     }
     g_pin_pool.give(extra);
+    return rc;
+}
+
+// ---- many sequences from one gate table in ONE pass (ff.concatenate_sequences; sequences.hip) ----------------
+namespace {
+
+struct SeqLayout {
+    size_t offsets, index, order, tau, omega, basis, U, tab, host, S, idx, inputs_end;    // one H2D
+    size_t Q, F, infid, outputs_end;                                                    // one D2H
+    size_t R, phases, L, end;                                                           // device only
+};
+
+SeqLayout seq_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W, size_t s_rows, int n_idx,
+                     size_t n_out) {
+    SeqLayout L;
+    const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.offsets = put(4*(size_t(P) + 1));
+    L.index = put(4*n_index);
+    L.order = put(4*size_t(P));
+    L.tau = put(8*size_t(T));
+    L.omega = put(8*size_t(W));
+    L.basis = put(16*size_t(N)*dd);
+    L.U = put(16*size_t(T)*dd);
+    L.tab = put(8*size_t(T));
+    L.host = put(row*size_t(n_host));
+    L.S = put(16*s_rows*W);
+    L.idx = put(4*size_t(n_idx));
+    L.inputs_end = o;
+    L.Q = put(16*size_t(P)*dd);
+    L.F = put(16*size_t(P)*A*A*W);
+    L.infid = put(8*size_t(P)*n_out);
+    L.outputs_end = o;
+    L.R = put(row*size_t(P));
+    L.phases = put(16*size_t(T)*W);
+    L.L = put(8*size_t(T)*N*N);
+    L.end = o;
+    return L;
+}
+
+size_t spectrum_rows(int s_ndim, int n_idx) {
+    return s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx);
+}
+
+}  // namespace
+
+size_t ffk_concatenate_sequences_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                                 int n_idx, int s_ndim) {
+    if (T < 1 || P < 1 || n_index < P || n_host < 0 || n_host > T || !ffk::sequences_supported(d, N, A) || W < 1)
+        return 0;
+    if (s_ndim != 0 && (s_ndim < 1 || s_ndim > 3 || n_idx < 1 || n_idx > A)) return 0;
+    const size_t n_out = s_ndim == 0 ? 0 : (s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx));
+    return seq_layout(T, P, size_t(n_index), n_host, d, A, N, W, s_ndim ? spectrum_rows(s_ndim, n_idx) : 0,
+                      s_ndim ? n_idx : 0, n_out).end;
+}
+
+int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const* gates, const int32_t* slots,
+                                       const double* gate_table, const double* gate_propagators, const double* tau,
+                                       int T, const int32_t* offsets, const int32_t* index, int P,
+                                       const double* omega, int W, const double* basis, int hermitian_basis, int d,
+                                       int A, int N, const double* spectrum, int s_ndim, int spectrum_is_real,
+                                       const int32_t* idx, int n_idx, int d_infidelity, double* total_propagators,
+                                       double** filter_function, double* infid) {
+    FFK_REQUIRE(result && gates && slots && gate_propagators && tau && offsets && index && omega && basis,
+                "NULL argument");
+    FFK_REQUIRE(total_propagators && filter_function, "NULL output argument");
+    FFK_REQUIRE(ffk::sequences_supported(d, N, A), "unsupported shape d=%d N=%d A=%d (need d = 2, N = 4, 1 <= A <= 4)",
+                d, N, A);
+    FFK_REQUIRE(hermitian_basis != 0, "the batched rule needs a Hermitian basis");
+    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 1,
+                "empty or oversized axis: T=%d P=%d W=%d", T, P, W);
+    FFK_REQUIRE(offsets[0] == 0, "offsets[0] = %d, expected 0", offsets[0]);
+    for (int p = 0; p < P; ++p)
+        FFK_REQUIRE(offsets[p + 1] > offsets[p], "offsets not increasing at sequence %d (%d -> %d)", p, offsets[p],
+                    offsets[p + 1]);
+    const size_t n_index = size_t(offsets[P]);
+    for (size_t g = 0; g < n_index; ++g)
+        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
+    size_t s_rows = 0, n_out = 0;
+    if (spectrum) {
+        FFK_REQUIRE(idx && infid && s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= A && d_infidelity >= 1 &&
+                    W >= 2, "bad spectrum arguments");
+        for (int i = 0; i < n_idx; ++i) FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "idx[%d] = %d outside [0, %d)", i, idx[i], A);
+        s_rows = spectrum_rows(s_ndim, n_idx);
+        n_out = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
+    } else {
+        n_idx = 0;
+    }
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    int n_host = 0;
+    for (int k = 0; k < T; ++k) {
+        const ffk_resident* g = gates[k];
+        if (!g) {
+            ++n_host;
+            continue;
+        }
+        FFK_REQUIRE(g != result, "gate %d: the result handle must not be an input", k);
+        FFK_REQUIRE(g->device == dev, "gate %d lives on device %d, current device is %d", k, g->device, dev);
+        FFK_REQUIRE(g->d == d && g->A == A && g->N == N && g->W == W,
+                    "gate %d: shape (d=%d, A=%d, N=%d, W=%d) differs from the pass's (d=%d, A=%d, N=%d, W=%d)", k,
+                    g->d, g->A, g->N, g->W, d, A, N, W);
+        if (slots[k] < 0)
+            FFK_REQUIRE(g->valid, "gate %d: no resident result in its handle", k);
+        else
+            FFK_REQUIRE(g->batch_valid && slots[k] < g->P, "gate %d: slot %d is no member of its handle", k, slots[k]);
+    }
+    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    const SeqLayout L = seq_layout(T, P, n_index, n_host, d, A, N, W, s_rows, n_idx, n_out);
+    result->valid = result->batch_valid = false;
+    if (result->device != dev || result->dev.size < L.end || result->pin.size < L.outputs_end) {
+        g_dev_pool.give(result->dev);
+        g_pin_pool.give(result->pin);
+        result->dev = result->pin = Block{nullptr, 0, -1};
+        if (int rc = g_dev_pool.take(L.end, dev, &result->dev)) return rc;
+        if (int rc = g_pin_pool.take(L.outputs_end, dev, &result->pin)) return rc;
+        result->device = dev;
+    }
+    unsigned char* hp = static_cast<unsigned char*>(result->pin.ptr);
+    unsigned char* dp = static_cast<unsigned char*>(result->dev.ptr);
+    const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
+    const auto clock0 = std::chrono::steady_clock::now();
+    // the sequences sorted by length, longest first (stable): the rule kernel deals them out in this order
+    std::vector<int32_t> order(P);
+    for (int p = 0; p < P; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [offsets](int32_t a, int32_t b) {
+        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
+    });
+    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
+    std::memcpy(hp + L.index, index, 4*n_index);
+    std::memcpy(hp + L.order, order.data(), 4*size_t(P));
+    std::memcpy(hp + L.tau, tau, 8*size_t(T));
+    std::memcpy(hp + L.omega, omega, 8*size_t(W));
+    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
+    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
+    // where each gate's control matrix lies on the device: in its own handle, or in the uploaded host table
+    int host_row = 0;
+    for (int k = 0; k < T; ++k) {
+        const ffk_resident* g = gates[k];
+        const unsigned char* at;
+        if (!g)
+            at = dp + L.host + row*size_t(host_row++);
+        else if (slots[k] < 0)
+            at = static_cast<const unsigned char*>(g->dev.ptr) + g->L.R;
+        else
+            at = static_cast<const unsigned char*>(g->dev.ptr) + g->batch_R + row*size_t(slots[k]);
+        std::memcpy(hp + L.tab + 8*size_t(k), &at, 8);
+    }
+    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    if (spectrum) {
+        double* hs = reinterpret_cast<double*>(hp + L.S);
+        if (spectrum_is_real) {
+            for (size_t i = 0; i < s_rows*W; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
+        } else {
+            std::memcpy(hs, spectrum, 16*s_rows*W);
+        }
+        std::memcpy(hp + L.idx, idx, 4*size_t(n_idx));
+    }
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    StreamDrain drain{s};
+    const auto clock1 = std::chrono::steady_clock::now();
+    auto at = [dp](size_t off) { return dp + off; };
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
+    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.index));
+    cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
+    double* dL = reinterpret_cast<double*>(at(L.L));
+    cplx* dF = reinterpret_cast<cplx*>(at(L.F));
+    FFK_HIP(ffk::launch_sequences_front(reinterpret_cast<const cplx*>(at(L.U)), reinterpret_cast<const double*>(at(L.tau)),
+                                        reinterpret_cast<const double*>(at(L.omega)), T, W, dOff, dIdx, P,
+                                        reinterpret_cast<const cplx*>(at(L.basis)), dPh, dL,
+                                        reinterpret_cast<cplx*>(at(L.Q)), s));
+    FFK_HIP(ffk::launch_sequences_rule(dPh, reinterpret_cast<const cplx* const*>(at(L.tab)), dL, dOff, dIdx,
+                                       reinterpret_cast<const int32_t*>(at(L.order)), P, T, A, W,
+                                       reinterpret_cast<cplx*>(at(L.R)), dF, s));
+    if (spectrum)
+        FFK_HIP(ffk::launch_infidelity_pulses(dF, A, W, P, reinterpret_cast<const cplx*>(at(L.S)), s_ndim,
+                                              reinterpret_cast<const double*>(at(L.omega)),
+                                              reinterpret_cast<const int32_t*>(at(L.idx)), n_idx, d_infidelity,
+                                              reinterpret_cast<double*>(at(L.infid)), s));
+    FFK_HIP(hipMemcpyAsync(hp + L.Q, dp + L.Q, L.outputs_end - L.Q, hipMemcpyDeviceToHost, s));
+    const auto clock2 = std::chrono::steady_clock::now();
+    FFK_HIP(hipStreamSynchronize(s));
+    const auto clock3 = std::chrono::steady_clock::now();
+    result->t_stage = std::chrono::duration<double>(clock1 - clock0).count();
+    result->t_enqueue = std::chrono::duration<double>(clock2 - clock1).count();
+    result->t_wait = std::chrono::duration<double>(clock3 - clock2).count();
+    if (int rc = kernel_fault_status()) return rc;
+    std::memcpy(total_propagators, hp + L.Q, 16*size_t(P)*dd);
+    *filter_function = reinterpret_cast<double*>(hp + L.F);
+    if (spectrum) std::memcpy(infid, hp + L.infid, 8*size_t(P)*n_out);
+    result->P = P; result->G = 1; result->d = d; result->W = W; result->N = N; result->A = A;
+    result->batch_R = L.R;
+    result->batch_F = L.F;
+    result->batch_omega = L.omega;
+    result->batch_valid = true;
+    return FFK_OK;
+}
+
+// The infidelity integral of a subset of a batched pass's members on their resident filter functions: ONE launch of
+// the pulse-axis integral (infid_pulses_kernel).  Runs of consecutive members are read in place; otherwise their
+// filter functions are first gathered by device-to-device copies.
+int ffk_resident_batch_infidelity(ffk_resident* r, const int32_t* members, int n_members, const double* spectrum,
+                                  int s_ndim, int spectrum_is_real, const int32_t* idx, int n_idx, int d,
+                                  double* infid) {
+    FFK_REQUIRE(r && r->batch_valid, "no resident batch result");
+    FFK_REQUIRE(members && spectrum && idx && infid, "NULL argument");
+    FFK_REQUIRE(n_members >= 1 && n_members <= 65535, "need 1 <= n_members <= 65535, got %d", n_members);
+    FFK_REQUIRE(s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= r->A && d >= 1 && r->W >= 2,
+                "bad spectrum arguments");
+    for (int i = 0; i < n_idx; ++i) FFK_REQUIRE(idx[i] >= 0 && idx[i] < r->A, "idx[%d] = %d outside [0, %d)", i, idx[i], r->A);
+    for (int m = 0; m < n_members; ++m)
+        FFK_REQUIRE(members[m] >= 0 && members[m] < r->P, "members[%d] = %d outside [0, %d)", m, members[m], r->P);
+    if (int rc = on_owning_device(r)) return rc;
+    const int W = r->W, A = r->A;
+    const size_t rows = spectrum_rows(s_ndim, n_idx);
+    const size_t n_out = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
+    const size_t fbytes = 16*size_t(A)*A*W;
+    bool consecutive = true;
+    for (int m = 1; m < n_members; ++m) consecutive = consecutive && members[m] == members[m - 1] + 1;
+    const size_t o_idx = align_up(16*rows*W), o_out = o_idx + align_up(4*size_t(n_idx));
+    const size_t stage = o_out + align_up(8*size_t(n_members)*n_out);
+    Block pin = {nullptr, 0, -1};
+    if (int rc = g_pin_pool.take(stage, r->device, &pin)) return rc;
+    unsigned char* hp = static_cast<unsigned char*>(pin.ptr);
+    double* hs = reinterpret_cast<double*>(hp);
+    if (spectrum_is_real) {
+        for (size_t i = 0; i < rows*W; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
+    } else {
+        std::memcpy(hs, spectrum, 16*rows*W);
+    }
+    std::memcpy(hp + o_idx, idx, 4*size_t(n_idx));
+    hipStream_t s;
+    int rc = resident_stream(&s);
+    if (!rc) {
+        std::lock_guard<std::mutex> lock(g_arena.mu);
+        void* base = nullptr;
+        rc = arena_reserve(stage + (consecutive ? 0 : align_up(fbytes*n_members)), &base);
+        if (!rc) {
+            auto run = [&]() -> int {
+                StreamDrain drain{s};
+                unsigned char* ws = static_cast<unsigned char*>(base);
+                const unsigned char* dp = static_cast<const unsigned char*>(r->dev.ptr);
+                FFK_HIP(hipMemcpyAsync(ws, hp, o_out, hipMemcpyHostToDevice, s));
+                const unsigned char* F = dp + r->batch_F + fbytes*size_t(members[0]);
+                if (!consecutive) {
+                    unsigned char* gathered = ws + stage;
+                    for (int m = 0; m < n_members;) {
+                        int e = m + 1;
+                        while (e < n_members && members[e] == members[e - 1] + 1) ++e;
+                        FFK_HIP(hipMemcpyAsync(gathered + fbytes*size_t(m), dp + r->batch_F + fbytes*size_t(members[m]),
+                                               fbytes*size_t(e - m), hipMemcpyDeviceToDevice, s));
+                        m = e;
+                    }
+                    F = gathered;
+                }
+                FFK_HIP(ffk::launch_infidelity_pulses(reinterpret_cast<const cplx*>(F), A, W, n_members,
+                                                      reinterpret_cast<const cplx*>(ws), s_ndim,
+                                                      reinterpret_cast<const double*>(dp + r->batch_omega),
+                                                      reinterpret_cast<const int32_t*>(ws + o_idx), n_idx, d,
+                                                      reinterpret_cast<double*>(ws + o_out), s));
+                FFK_HIP(hipMemcpyAsync(hp + o_out, ws + o_out, 8*size_t(n_members)*n_out, hipMemcpyDeviceToHost, s));
+                FFK_HIP(hipStreamSynchronize(s));
+                return FFK_OK;
+            };
+            rc = run();
+        }
+    }
+    if (!rc) rc = kernel_fault_status();
+    if (!rc) std::memcpy(infid, hp + o_out, 8*size_t(n_members)*n_out);
+    g_pin_pool.give(pin);
     return rc;
 }
 

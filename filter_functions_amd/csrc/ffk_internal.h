@@ -356,6 +356,21 @@ hipError_t launch_sequence_front(const cplx* U, const int32_t* index, int G, int
                                  const double* omega, int T, int W, cplx* phases, double* omega_copy,
                                  hipStream_t stream, double* Lpulse = nullptr);
 
+// ---- sequences.hip ----------------------------------------------------------------------------
+// Many sequences from one table of T distinct gates (d = 2, N = 4, A <= 4), CSR offsets (P + 1) / index.
+// Front: phases (T, W) = exp(i omega tau_k), Lpulse (T, N, N) f64 (Hermitian basis), Qtot (P, d, d) each
+// sequence's total propagator.  Rule: R (P, A, N, W) and F (P, A, A, W); Rtab: T device pointers to the gates'
+// control matrices (A, N, W); order (P): the sequences sorted by length, longest first.
+bool sequences_supported(int d, int N, int A);
+bool sequences_staged(int T, int A);
+int sequences_groups(int P, int W, int A, bool staged);
+hipError_t launch_sequences_front(const cplx* U, const double* tau, const double* omega, int T, int W,
+                                  const int32_t* offsets, const int32_t* index, int P, const cplx* basis,
+                                  cplx* phases, double* Lpulse, cplx* Qtot, hipStream_t stream);
+hipError_t launch_sequences_rule(const cplx* phases, const cplx* const* Rtab, const double* Lpulse,
+                                 const int32_t* offsets, const int32_t* index, const int32_t* order, int P, int T,
+                                 int A, int W, cplx* R, cplx* F, hipStream_t stream);
+
 // ---- decay.hip -------------------------------------------------------------------------------
 // Gamma (Gp,Gp,n_idx[,n_idx],N,N) f64 from R (Gp,A,N,W) c128 (Gp = 1: the total control matrix),
 // S c128 (W,), (n_idx,W) or (n_idx,n_idx,W); omega (Wg,) is the global grid of which R and S hold

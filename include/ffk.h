@@ -604,6 +604,35 @@ int ffk_resident_batch_filter_function_infidelity(ffk_resident* handle, int P, c
                                                   double* infidelity, int32_t* n_failed);
 int ffk_resident_batch_control_matrix(ffk_resident* handle, int pulse, double* control_matrix);
 
+/* ---- many gate sequences from one table of distinct gates in ONE pass (ff.concatenate_sequences) ----
+ * P sequences as a CSR list: offsets (P + 1) int32 host, offsets[0] = 0 and strictly increasing, index
+ * (offsets[P]) int32 host, each entry in [0, T).  The T gates: gates[k] an ffk_resident* whose control matrix
+ * (A, N, W) is read in place -- slots[k] < 0 for a single resident result, slots[k] >= 0 for member slots[k] of a
+ * batched or sequence pass -- or NULL: the gate's control matrix is the next row of gate_table (n_host, A, N, W)
+ * c128 host, in gate order.  gate_propagators (T, d, d) c128 and tau (T,) f64 host: the gates' total propagators
+ * and durations; omega (W,) f64, basis (N, d, d) c128.  Supported: d = 2, N = 4, 1 <= A <= 4, Hermitian basis.
+ * Results stay in `result` (not one of the gates): the control matrices (P, A, N, W) in HBM
+ * (ffk_resident_batch_control_matrix copies member p's out), the filter functions (P, A, A, W) in HBM and in
+ * pinned host memory (*filter_function points there until the handle is reused or destroyed); the total
+ * propagators (P, d, d) c128 go to the caller's array.  Optional (spectrum != NULL): the infidelities (P, n_idx
+ * [, n_idx]) of every sequence on a shared spectrum, as in ffk_resident_batch_filter_function_infidelity.
+ * A sequence's results do not depend on the other sequences of the pass.  Bad arguments: FFK_EINVAL. */
+size_t ffk_concatenate_sequences_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                                 int n_idx, int s_ndim);
+int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const* gates, const int32_t* slots,
+                                       const double* gate_table, const double* gate_propagators, const double* tau,
+                                       int T, const int32_t* offsets, const int32_t* index, int P,
+                                       const double* omega, int W, const double* basis, int hermitian_basis, int d,
+                                       int A, int N, const double* spectrum, int s_ndim, int spectrum_is_real,
+                                       const int32_t* idx, int n_idx, int d_infidelity, double* total_propagators,
+                                       double** filter_function, double* infidelity);
+/* The infidelities (n_members, n_idx[, n_idx]) of members (n_members,) int32 of a batched or sequence pass on their
+ * resident filter functions, ONE launch of the pulse-axis integral; spectrum, idx and d as in
+ * ffk_resident_infidelity.  Needs W >= 2 and n_members <= 65535. */
+int ffk_resident_batch_infidelity(ffk_resident* handle, const int32_t* members, int n_members, const double* spectrum,
+                                  int s_ndim, int spectrum_is_real, const int32_t* idx, int n_idx, int d,
+                                  double* infidelity);
+
 /* ---- one-sided all-gather of the F blocks over xGMI (frequency-sharded step; the
  *      reference has no multi-device path: numeric.py:846-869 is embarrassingly parallel in omega
  *      and this is the exchange that reassembles F(omega) for util.integrate, util.py:880-906) ----

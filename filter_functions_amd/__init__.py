@@ -13,11 +13,12 @@ The arithmetic runs in hand-written HIP kernels for gfx950 behind a C ABI
 side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
-from . import analytic, basis, batch, gradient, numeric, pulse_sequence, sequences, superoperator, util
+from . import analytic, basis, batch, gradient, numeric, processes, pulse_sequence, sequences, superoperator, util
 from .basis import Basis
 from .batch import get_filter_functions, infidelities
 from .gradient import infidelity_derivative
 from .numeric import error_transfer_matrix, infidelity
+from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
 from .sequences import concatenate_sequences
 from .pulse_sequence import (PulseSequence, concatenate, concatenate_periodic,
                              concatenate_without_filter_function, extend, remap)
@@ -25,10 +26,10 @@ from .superoperator import liouville_representation
 
 __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'concatenate', 'concatenate_periodic',
            'concatenate_sequences',
-           'concatenate_without_filter_function',
-           'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
+           'concatenate_without_filter_function', 'cumulant_functions', 'decay_amplitudes',
+           'error_transfer_matrices', 'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
            'infidelity_derivative',
-           'liouville_representation', 'numeric',
+           'liouville_representation', 'numeric', 'processes',
            'pulse_sequence', 'remap', 'sequences', 'superoperator', 'util']
 
 __version__ = '0.1.0'

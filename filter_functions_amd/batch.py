@@ -47,6 +47,11 @@ class BatchResult:
     def __reduce__(self):
         return (type(None), ())
 
+    @property
+    def handle(self):
+        """The ``ffk_resident*`` (for calls that read the members' control matrices in place)."""
+        return self._handle
+
     def evaluate(self, c_opers, c_coeffs, dt, t, omega, basis, n_opers, n_coeffs, spectrum=None, idx=None,
                  d_infidelity=None):
         """One batched pass over the stacked per-pulse arrays (leading axis P).  Returns (eigvals,
@@ -157,9 +162,10 @@ def split_passes(members, per_pulse, budget=PASS_BYTES, max_pulses=MAX_PULSES):
     return [members[a:b] for a, b in zip(bounds[:-1], bounds[1:])]
 
 
-def _run_pass(pulses, members, omega, basis, spectrum=None, idx=None):
-    """One batched pass over ``pulses[i] for i in members``; fills their caches.  Returns the
-    infidelities (P, ...) or None."""
+def _run_pass(pulses, members, omega, basis, spectrum=None, idx=None, keep_filter_function=True):
+    """One batched pass over ``pulses[i] for i in members``; fills their caches.  Returns the filter functions
+    (P, A, A, W) and the infidelities (P, ...) or None.  *keep_filter_function* False leaves the filter function
+    out of the members' caches: what ``pulse.cache_control_matrix(omega)`` leaves."""
     group = [pulses[i] for i in members]
     stack = lambda f: np.stack([f(p) for p in group])      # noqa: E731
     batch = BatchResult()
@@ -179,7 +185,8 @@ def _run_pass(pulses, members, omega, basis, spectrum=None, idx=None):
     for j, pulse in enumerate(group):
         pulse._data.update(eigvals=D[j], eigvecs=V[j], propagators=Q[j], total_propagator=Q[j][-1])
         pulse._frequency_data['control_matrix'] = Deferred(functools.partial(batch.control_matrix, j), nbytes)
-        pulse._frequency_data['filter_function'] = F[j]
+        if keep_filter_function:
+            pulse._frequency_data['filter_function'] = F[j]
         pulse._defer_by_products()
         pulse._resident = _Member(batch, j)
     return F, infid

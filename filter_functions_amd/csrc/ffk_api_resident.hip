@@ -1110,6 +1110,174 @@ int ffk_resident_batch_infidelity(ffk_resident* r, const int32_t* members, int n
     return rc;
 }
 
+// ---- decay amplitudes, cumulant functions and error transfer matrices of many pulses in ONE pass, their control
+//      matrices read where they lie in HBM (ff.decay_amplitudes, ff.cumulant_functions, ff.error_transfer_matrices;
+//      processes.hip) ----------------------------------------------------------------------------------------------
+namespace {
+
+struct ProcLayout {
+    size_t tab, omega, basis, S, idx, host, inputs_end;           // one H2D
+    size_t outputs, gamma, K, U, flags, outputs_end;              // one D2H of [outputs, outputs_end)
+    size_t scale, partials, cumulant, end;                        // device only
+};
+
+// The requested results lie next to each other in front of the flags; what is only an intermediate of this call lies
+// behind them with the workspace.  stage: 1 decay amplitudes, 2 + cumulant function, 3 + error transfer matrix.
+ProcLayout proc_layout(int P, int n_host, int A, int N, int W, int d, int n_idx, int s_ndim, bool single_qubit,
+                       bool want_gamma, bool want_K, bool want_U) {
+    ProcLayout L;
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N;
+    const size_t pairs = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
+    const size_t s_rows = spectrum_rows(s_ndim, n_idx);
+    const int stage = want_U ? 3 : (want_K ? 2 : 1);
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.tab = put(8*size_t(P));
+    L.omega = put(8*size_t(W));
+    L.basis = put(16*size_t(N)*dd);
+    L.S = put(16*s_rows*W);
+    L.idx = put(4*size_t(n_idx));
+    L.host = put(16*size_t(A)*N*W*size_t(n_host));
+    L.inputs_end = o;
+    L.outputs = o;
+    L.gamma = L.K = L.U = 0;
+    if (want_gamma) L.gamma = put(8*size_t(P)*pairs*nn);
+    if (want_K) L.K = put(8*size_t(P)*pairs*nn);
+    if (want_U) L.U = put(8*size_t(P)*nn);
+    L.flags = put(4*size_t(P));
+    L.outputs_end = o;
+    if (!want_gamma) L.gamma = put(8*size_t(P)*pairs*nn);
+    if (!want_K && stage >= 2) L.K = put(8*size_t(P)*pairs*nn);
+    L.scale = put(16*s_rows*W);
+    const int chunks = ffk::processes_decay_chunks(W, nullptr);
+    L.partials = put(chunks > 1 ? 8*size_t(chunks)*P*pairs*nn : 0);
+    L.cumulant = put(stage >= 2 && !single_qubit ? ffk::cumulant_workspace_bytes(size_t(P)*pairs, N, d) : 0);
+    L.end = o;
+    return L;
+}
+
+bool proc_shape_ok(int P, int n_host, int A, int N, int W, int d, int n_idx, int s_ndim) {
+    return P >= 1 && P <= 65535 && n_host >= 0 && n_host <= P && A >= 1 && N >= 1 && N <= 16 && W >= 1 &&
+           d_templated_ok(d) && N <= d*d && s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= A;
+}
+
+}  // namespace
+
+size_t ffk_resident_batch_processes_workspace_bytes(int P, int n_host, int A, int N, int W, int d, int n_idx,
+                                                    int s_ndim) {
+    if (!proc_shape_ok(P, n_host, A, N, W, d, n_idx, s_ndim)) return 0;
+    return proc_layout(P, n_host, A, N, W, d, n_idx, s_ndim, false, true, true, true).end;
+}
+
+int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slots, const double* control_matrices,
+                                 int P, int A, int N, int W, int d, const double* omega, const double* basis,
+                                 int single_qubit, const double* spectrum, int s_ndim, const int32_t* idx, int n_idx,
+                                 double* decay_amplitudes, double* cumulant_function, double* error_transfer_matrix,
+                                 int32_t* not_finite) {
+    FFK_REQUIRE(pulses && slots && omega && basis && spectrum && idx, "NULL argument");
+    FFK_REQUIRE(decay_amplitudes || cumulant_function || error_transfer_matrix, "no output requested");
+    FFK_REQUIRE(!error_transfer_matrix || not_finite, "not_finite is NULL but the error transfer matrices are requested");
+    FFK_REQUIRE(proc_shape_ok(P, 0, A, N, W, d, n_idx, s_ndim),
+                "unsupported shape P=%d A=%d N=%d W=%d d=%d n_idx=%d s_ndim=%d (need 1 <= P <= 65535, N <= 16, "
+                "N <= d^2, 1 <= n_idx <= A, 1 <= s_ndim <= 3)", P, A, N, W, d, n_idx, s_ndim);
+    FFK_REQUIRE(!single_qubit || (d == 2 && N == 4), "single-qubit expression needs d = 2, N = 4");
+    for (int i = 0; i < n_idx; ++i) FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "idx[%d] = %d outside [0, %d)", i, idx[i], A);
+    const size_t pairs = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
+    const bool want_gamma = decay_amplitudes != nullptr, want_K = cumulant_function != nullptr;
+    const bool want_U = error_transfer_matrix != nullptr;
+    const int stage = want_U ? 3 : (want_K ? 2 : 1);
+    FFK_REQUIRE(stage < 2 || single_qubit || size_t(P)*pairs <= 65535,
+                "%d pulses of %zu operator pairs exceed the 65535 cumulant functions of one launch", P, pairs);
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    int n_host = 0;
+    for (int p = 0; p < P; ++p) {
+        const ffk_resident* g = pulses[p];
+        if (!g) {
+            ++n_host;
+            continue;
+        }
+        FFK_REQUIRE(g->device == dev, "pulse %d lives on device %d, current device is %d", p, g->device, dev);
+        FFK_REQUIRE(g->A == A && g->N == N && g->W == W,
+                    "pulse %d: shape (A=%d, N=%d, W=%d) differs from the pass's (A=%d, N=%d, W=%d)", p, g->A, g->N,
+                    g->W, A, N, W);
+        if (slots[p] < 0)
+            FFK_REQUIRE(g->valid, "pulse %d: no resident result in its handle", p);
+        else
+            FFK_REQUIRE(g->batch_valid && slots[p] < g->P, "pulse %d: slot %d is no member of its handle", p, slots[p]);
+    }
+    FFK_REQUIRE(n_host == 0 || control_matrices, "control_matrices is NULL but %d pulse(s) have no handle", n_host);
+    const ProcLayout L = proc_layout(P, n_host, A, N, W, d, n_idx, s_ndim, single_qubit != 0, want_gamma, want_K,
+                                     want_U);
+    const size_t s_rows = spectrum_rows(s_ndim, n_idx), dd = size_t(d)*d, nn = size_t(N)*N;
+    const size_t row = 16*size_t(A)*N*W, out_bytes = L.outputs_end - L.outputs;
+    // a spectrum of one or two dimensions with an imaginary part: Gamma is not symmetric, every weight is complex
+    int complex_weights = 0;
+    if (s_ndim != 3)
+        for (size_t i = 0; i < s_rows*W && !complex_weights; ++i) complex_weights = spectrum[2*i + 1] != 0.0;
+    Block pin = {nullptr, 0, -1};
+    if (int rc = g_pin_pool.take(L.outputs_end, dev, &pin)) return rc;
+    unsigned char* hp = static_cast<unsigned char*>(pin.ptr);
+    auto run = [&]() -> int {
+        hipStream_t s;
+        if (int rc = resident_stream(&s)) return rc;
+        std::lock_guard<std::mutex> lock(g_arena.mu);
+        void* base = nullptr;
+        if (int rc = arena_reserve(L.end, &base)) return rc;
+        unsigned char* dp = static_cast<unsigned char*>(base);
+        // where each pulse's control matrix lies on the device: in its handle, or in the uploaded host table
+        int host_row = 0;
+        for (int p = 0; p < P; ++p) {
+            const ffk_resident* g = pulses[p];
+            const unsigned char* at;
+            if (!g)
+                at = dp + L.host + row*size_t(host_row++);
+            else if (slots[p] < 0)
+                at = static_cast<const unsigned char*>(g->dev.ptr) + g->L.R;
+            else
+                at = static_cast<const unsigned char*>(g->dev.ptr) + g->batch_R + row*size_t(slots[p]);
+            std::memcpy(hp + L.tab + 8*size_t(p), &at, 8);
+        }
+        std::memcpy(hp + L.omega, omega, 8*size_t(W));
+        std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
+        std::memcpy(hp + L.S, spectrum, 16*s_rows*W);
+        std::memcpy(hp + L.idx, idx, 4*size_t(n_idx));
+        if (n_host) std::memcpy(hp + L.host, control_matrices, row*size_t(n_host));
+        StreamDrain drain{s};
+        FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+        const cplx* dS = reinterpret_cast<const cplx*>(dp + L.S);
+        const double* dOmega = reinterpret_cast<const double*>(dp + L.omega);
+        const int32_t* dIdx = reinterpret_cast<const int32_t*>(dp + L.idx);
+        cplx* dScale = reinterpret_cast<cplx*>(dp + L.scale);
+        double* dGamma = reinterpret_cast<double*>(dp + L.gamma);
+        double* dK = reinterpret_cast<double*>(dp + L.K);
+        int32_t* dFlags = reinterpret_cast<int32_t*>(dp + L.flags);
+        FFK_HIP(hipMemsetAsync(dFlags, 0, 4*size_t(P), s));
+        FFK_HIP(ffk::launch_spectral_weights(dS, int(s_rows), W, dOmega, W, 0, dScale, s));
+        FFK_HIP(ffk::launch_processes_decay(reinterpret_cast<const cplx* const*>(dp + L.tab), P, N, W, dScale, s_ndim,
+                                            complex_weights, dIdx, n_idx, dGamma,
+                                            reinterpret_cast<double*>(dp + L.partials), s));
+        if (stage >= 2)
+            FFK_HIP(ffk::launch_cumulant_function(dGamma, size_t(P)*pairs, N, d,
+                                                  reinterpret_cast<const cplx*>(dp + L.basis), single_qubit, dK,
+                                                  dp + L.cumulant, s));
+        if (stage >= 3)
+            FFK_HIP(ffk::launch_processes_expm(dK, P, int(pairs), N, reinterpret_cast<double*>(dp + L.U), dFlags, s));
+        FFK_HIP(hipMemcpyAsync(hp + L.outputs, dp + L.outputs, out_bytes, hipMemcpyDeviceToHost, s));
+        FFK_HIP(hipStreamSynchronize(s));
+        return kernel_fault_status();
+    };
+    const int rc = run();
+    if (!rc) {
+        if (want_gamma) std::memcpy(decay_amplitudes, hp + L.gamma, 8*size_t(P)*pairs*nn);
+        if (want_K) std::memcpy(cumulant_function, hp + L.K, 8*size_t(P)*pairs*nn);
+        if (want_U) std::memcpy(error_transfer_matrix, hp + L.U, 8*size_t(P)*nn);
+        if (not_finite) std::memcpy(not_finite, hp + L.flags, 4*size_t(P));
+    }
+    g_pin_pool.give(pin);
+    return rc;
+}
+
 }  // extern "C"
 
 #if defined(FFK_HOST_SANITIZE)

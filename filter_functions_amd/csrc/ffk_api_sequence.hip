@@ -497,14 +497,7 @@ int ffk_cumulant_function(const double* decay_amplitudes, int batch, int N, int 
 // ---------------------------------------------------------------------------------------------
 namespace {
 // |B|_1 <= 1/2 after s halvings (launch_expm_real's Taylor polynomial is sized for that)
-int squarings_for(double norm) {
-    int squarings = 0;
-    while (norm > 0.5 && squarings < 64) {
-        norm *= 0.5;
-        ++squarings;
-    }
-    return squarings;
-}
+int squarings_for(double norm) { return ffk::expm_squarings(norm); }
 }  // namespace
 
 int ffk_expm_real(const double* matrix, int N, double* result) {

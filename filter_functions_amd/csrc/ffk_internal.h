@@ -451,6 +451,30 @@ hipError_t launch_sum_and_one_norm(const double* K, int batch, int N, double* su
 // exp of a real N x N matrix (device pointers; w: five N*N scratch matrices); see decay.hip
 hipError_t launch_expm_real(const double* A, int N, int squarings, double* out, double* const w[5],
                             hipStream_t stream);
+// halvings s after which |A / 2^s|_1 <= 1/2 (launch_expm_real's Taylor polynomial is sized for that)
+__host__ __device__ inline int expm_squarings(double norm) {
+    int squarings = 0;
+    while (norm > 0.5 && squarings < 64) {
+        norm *= 0.5;
+        ++squarings;
+    }
+    return squarings;
+}
+
+// ---- processes.hip ---------------------------------------------------------------------------
+// Gamma (P, pairs, N, N) f64 of P independent pulses, N <= 16, pairs = n_idx (s_ndim 1, 2) or n_idx^2 (3), from
+// Rtab: P device pointers to control matrices (A, N, W); scale from launch_spectral_weights (rows of W);
+// complex_weights: some weight has an imaginary part.  The frequency axis is cut into
+// processes_decay_chunks(W) chunks (a function of W alone); with more than one, partials holds
+// (chunks, P, pairs, N, N) doubles.
+int processes_decay_chunks(int W, int* chunk_length);
+hipError_t launch_processes_decay(const cplx* const* Rtab, int P, int N, int W, const cplx* scale, int s_ndim,
+                                  int complex_weights, const int32_t* idx, int n_idx, double* gamma,
+                                  double* partials, hipStream_t stream);
+// out (P, N, N) = exp(sum over the rows of K (P, rows, N, N)), N <= 16, squarings chosen on the device;
+// not_finite (P): 1 where the sum holds a NaN or Inf (nothing is written for that pulse)
+hipError_t launch_processes_expm(const double* K, int P, int rows, int N, double* out, int32_t* not_finite,
+                                 hipStream_t stream);
 
 // ---- generic.hip (17 <= d <= kMaxDGeneric) -----------------------------------------------------
 bool generic_dimension(int d);

@@ -125,17 +125,23 @@ class _SequenceMember:
         return (type(None), ())
 
 
-def _gate_source(gate, W, A):
-    """(handle, slot) of the HBM copy of *gate*'s control matrix, or None (a host array)."""
-    res = gate._resident
-    if isinstance(res, ResidentResult) and res.shape is not None and res.shape[1:] == (2, W, 4, A):
+def resident_source(pulse, d, W, N, A):
+    """(handle, slot) of the HBM copy of *pulse*'s control matrix of shape (A, N, W) -- slot -1: a single resident
+    result; else the member of a batched or sequence pass --, or None (a host array, or nothing resident)."""
+    res = pulse._resident
+    if isinstance(res, ResidentResult) and res.shape is not None and res.shape[1:] == (d, W, N, A):
         return res.handle, -1
     if isinstance(res, _Member) and res.slot is not None and res.batch.shape is not None \
-            and res.batch.shape[2:] == (2, W, 4, A):
+            and res.batch.shape[2:] == (d, W, N, A):
         return res.batch.handle, res.slot
-    if isinstance(res, _SequenceMember) and res.batch.shape[1:] == (W, 4, A):
+    if isinstance(res, _SequenceMember) and d == 2 and res.batch.shape[1:] == (W, N, A):
         return res.batch.handle, res.slot
     return None
+
+
+def _gate_source(gate, W, A):
+    """(handle, slot) of the HBM copy of single-qubit *gate*'s control matrix, or None (a host array)."""
+    return resident_source(gate, 2, W, 4, A)
 
 
 def _plan(pulses, distinct, first, index, calc_filter_function, which, omega):

@@ -633,6 +633,31 @@ int ffk_resident_batch_infidelity(ffk_resident* handle, const int32_t* members, 
                                   int s_ndim, int spectrum_is_real, const int32_t* idx, int n_idx, int d,
                                   double* infidelity);
 
+/* ---- decay amplitudes, cumulant functions and error transfer matrices of P independent pulses in ONE pass
+ *      (ff.decay_amplitudes, ff.cumulant_functions, ff.error_transfer_matrices) ----
+ * The control matrix (A, N, W) of pulse p is read in place: pulses[p] an ffk_resident* with slots[p] < 0 for a
+ * single resident result, slots[p] >= 0 for member slots[p] of a batched or sequence pass -- or NULL: the next row
+ * of control_matrices (n_host, A, N, W) c128 host, in pulse order (may be NULL if no pulse is NULL).  omega (W,)
+ * f64, basis (N, d, d) c128, spectrum c128 (W,), (n_idx, W) or (n_idx, n_idx, W) and idx (n_idx,) int32 as for
+ * ffk_decay_amplitudes, all host.  Supported: N <= 16, N <= d^2, 2 <= d <= FFK_MAX_D_TEMPLATED, 1 <= P <= 65535
+ * (and P * pairs <= 65535 cumulant functions unless single_qubit; pairs = n_idx, or n_idx^2 for s_ndim = 3).
+ * Outputs, host, each may be NULL (only the stages a requested output needs are run): decay_amplitudes and
+ * cumulant_function (P, n_idx[, n_idx], N, N) f64 -- a pulse's values are those of ffk_decay_amplitudes with
+ * n_pulses = 1 up to the order of the sum over the frequencies, and of ffk_cumulant_function (single_qubit as
+ * there) --, error_transfer_matrix (P, N, N) f64 = exp of the cumulant function summed over the noise operators,
+ * with the arithmetic of ffk_expm_real and the number of squarings chosen on the device.  not_finite (P,) int32
+ * (required with error_transfer_matrix): 1 where that sum holds a NaN or Inf; the pulse's error transfer matrix
+ * is then not written.  A pulse's results do not depend on the other pulses of the pass.  One H2D copy of the small
+ * inputs and the host rows, one D2H copy of the requested outputs, no synchronisation in between.  Bad
+ * arguments: FFK_EINVAL.  The query returns the device bytes a pass with all three outputs holds (0: unsupported). */
+size_t ffk_resident_batch_processes_workspace_bytes(int P, int n_host, int A, int N, int W, int d, int n_idx,
+                                                    int s_ndim);
+int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slots, const double* control_matrices,
+                                 int P, int A, int N, int W, int d, const double* omega, const double* basis,
+                                 int single_qubit, const double* spectrum, int s_ndim, const int32_t* idx, int n_idx,
+                                 double* decay_amplitudes, double* cumulant_function, double* error_transfer_matrix,
+                                 int32_t* not_finite);
+
 /* ---- one-sided all-gather of the F blocks over xGMI (frequency-sharded step; the
  *      reference has no multi-device path: numeric.py:846-869 is embarrassingly parallel in omega
  *      and this is the exchange that reassembles F(omega) for util.integrate, util.py:880-906) ----

@@ -13,9 +13,11 @@ The arithmetic runs in hand-written HIP kernels for gfx950 behind a C ABI
 side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
-from . import analytic, basis, batch, gradient, numeric, processes, pulse_sequence, sequences, superoperator, util
+from . import (analytic, basis, batch, batch_gradient, gradient, numeric, processes, pulse_sequence, sequences,
+               superoperator, util)
 from .basis import Basis
 from .batch import get_filter_functions, infidelities
+from .batch_gradient import filter_function_derivatives, infidelity_derivatives
 from .gradient import infidelity_derivative
 from .numeric import error_transfer_matrix, infidelity
 from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
@@ -24,11 +26,12 @@ from .pulse_sequence import (PulseSequence, concatenate, concatenate_periodic,
                              concatenate_without_filter_function, extend, remap)
 from .superoperator import liouville_representation
 
-__all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'concatenate', 'concatenate_periodic',
+__all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradient', 'concatenate',
+           'concatenate_periodic',
            'concatenate_sequences',
            'concatenate_without_filter_function', 'cumulant_functions', 'decay_amplitudes',
            'error_transfer_matrices', 'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
-           'infidelity_derivative',
+           'filter_function_derivatives', 'infidelity_derivative', 'infidelity_derivatives',
            'liouville_representation', 'numeric', 'processes',
            'pulse_sequence', 'remap', 'sequences', 'superoperator', 'util']
 

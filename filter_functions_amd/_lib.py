@@ -206,6 +206,12 @@ SIGNATURES = {
                                        c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     'ffk_eigensolver_status_batch_dev': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'ffk_batch_filter_function_derivative_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int,
+                                                                        c_int]),
+    'ffk_batch_filter_function_derivative_chunk': (c_int, [c_int, c_int, c_int]),
+    'ffk_batch_filter_function_derivative': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                                     c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                     c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'ffk_kernel_fault_status': (c_int, [POINTER(c_int32), c_int]),
     'ffk_resident_create': (c_int, [POINTER(c_void_p)]),
     'ffk_resident_destroy': (c_int, [c_void_p]),

@@ -440,6 +440,23 @@ hipError_t launch_filter_function_derivative_from_control_matrix(const cplx* R, 
 hipError_t launch_infidelity_derivative(const double* dF, int A, int G, int H, int W, const cplx* scale,
                                         int s_ndim, int d, double* out, hipStream_t stream);
 
+// ---- grad_batch.hip (P pulses of one shape, 2 <= d <= 4, A <= 4, H <= 8) ------------------------
+// Segments per chunk of the batched gradient pass: a function of the shape, never of P.
+int grad_batch_chunk(int G, int d, int W);
+bool grad_batch_supported(int P, int W, int A, int H, int G, int d);
+// complex numbers of one segment's record [T, Bbar (A), Abar (H), E (H)]
+size_t grad_batch_record_elems(int d, int A, int H);
+// Every per-pulse array pulse-major: eigvals (P,G,d), eigvecs (P,G,d,d), propagators (P,G+1,d,d), n_opers (P,A,d,d),
+// n_coeffs (P,A,G), c_opers (P,H,d,d), ratio (P,A,H,G) or NULL, dt (P,G), t (P,G+1); omega (W) and scale (from
+// launch_spectral_weights, rows = 1 or A) shared.  Scratch: rec (P G record_elems), totals (P,C,A,d,d,W) with
+// C = ceil(G / chunk), ytot (P,A,d,d,W), partial (ceil(W/64), P,A,G,H) doubles (only with dI).  Outputs, either may
+// be NULL: dF (P,A,G,H,W), dI (P,A,G,H).  Five launches (four without dI), whatever P.
+hipError_t launch_grad_batch(int P, const double* eigvals, const cplx* eigvecs, const cplx* propagators,
+                             const double* omega, int W, const cplx* n_opers, int A, const double* n_coeffs,
+                             const cplx* c_opers, int H, const double* ratio, const double* dt, const double* t,
+                             int G, int d, const cplx* scale, int s_ndim, cplx* rec, cplx* totals, cplx* ytot,
+                             double* partial, double* dF, double* dI, hipStream_t stream);
+
 // B (W,A,d,d) = B^(0) + sum_g phases[g-1] P_{g-1}^dag B^(g) P_{g-1}; atomic (G,W,A,d,d), props (G-1,d,d)
 hipError_t launch_noise_ops_from_atomic(const cplx* phases, const cplx* atomic, const cplx* props,
                                         int G, int W, int A, int d, cplx* out, hipStream_t stream);

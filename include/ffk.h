@@ -515,6 +515,32 @@ int ffk_pipeline_batch_dev(int P, const double* c_opers, int n_cops, const doubl
 int ffk_eigensolver_status_batch_dev(const void* workspace, size_t workspace_bytes, int P, int G, int d,
                                      int32_t* n_failed, void* stream);
 
+/* ---- batched gradient: P pulses of one shape (d, G, A, H) in ONE pass (ff.infidelity_derivatives /
+ *      ff.filter_function_derivatives) --------------------------------------------------------------------------
+ * ffk_filter_function_derivative for P pulses at once, 2 <= d <= 4, A <= 4, H <= 8, 1 <= P <= 65535.  Every per-pulse
+ * array is pulse-major with a leading axis P: eigvals (P, G, d), eigvecs (P, G, d, d), propagators (P, G+1, d, d),
+ * n_opers (P, A, d, d), n_coeffs (P, A, G), c_opers (P, H, d, d), n_coeffs_ratio (P, A, H, G) or NULL, dt (P, G),
+ * t (P, G+1).  Shared by all pulses: omega (W,) and spectrum (W,) or (A, W) c128 (s_ndim 1, 2).  Outputs, either may
+ * be NULL but not both: filter_function_derivative (P, A, G, H, W) f64, infidelity_derivative (P, A, G, H) f64.
+ * The inputs cross in one copy from a pinned staging block, the results in one copy per requested output, nothing
+ * synchronises in between, and the number of launches and copies does not depend on P.  The running sums of the
+ * interaction-picture noise operators (G, A, d, d, W per pulse on the single path) are never formed: the pass keeps
+ * the sums of chunks of L = ffk_batch_filter_function_derivative_chunk(G, d, W) segments, ceil(G/L) <= 16 per pulse,
+ * and the gradient kernel rebuilds the running sum in registers as it walks a chunk.  L depends on the shape only,
+ * never on P: a pulse's result is the same bits in every batch.  With only the infidelity derivative requested the
+ * filter-function derivative is never stored either.
+ * The two queries run without a GPU.  ..._workspace_bytes: device bytes of a pass (exactly linear in P; 0 for a
+ * shape the pass does not take); the call reserves them in the library's arena itself.                           */
+size_t ffk_batch_filter_function_derivative_workspace_bytes(int P, int W, int A, int H, int G, int d, int want_dF);
+int ffk_batch_filter_function_derivative_chunk(int G, int d, int W);
+int ffk_batch_filter_function_derivative(int P, const double* eigvals, const double* eigvecs,
+                                         const double* propagators, const double* omega, int W,
+                                         const double* n_opers, int A, const double* n_coeffs,
+                                         const double* c_opers, int H, const double* n_coeffs_ratio,
+                                         const double* dt, const double* t, int G, int d, const double* spectrum,
+                                         int s_ndim, double* filter_function_derivative,
+                                         double* infidelity_derivative);
+
 /* Fault word of the kernels whose wavefronts hand tiles to one another through flags in LDS (the d = 4
  * accumulation behind ffk_control_matrix*, ffk_pipeline_dev and the resident passes; reference loop
  * numeric.py:846-869).  Their waits are bounded; a wait that runs out stores a non-zero code in a word of mapped

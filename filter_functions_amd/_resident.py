@@ -85,16 +85,25 @@ def _view(address, count, dtype, shape, owner):
     return np.ctypeslib.as_array(buf).view(dtype).reshape(shape)
 
 
-class ResidentResult:
-    """Owns one ``ffk_resident`` handle: the device-resident control matrix, filter function and
-    frequency grid of one pass, and the pinned host block the small results live in."""
+def spectrum_arguments(spectrum, idx):
+    """What the library takes of a validated spectrum (``util.parse_spectrum``) and the noise-operator
+    indices *idx*: (spectrum as f64 or c128, whether it is real, idx as int32, shape of one pulse's integrals)."""
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    real = not np.iscomplexobj(spectrum)
+    S = as_f64(spectrum) if real else as_c128(spectrum)
+    n_idx = len(idx)
+    return S, int(real), idx, (n_idx, n_idx) if S.ndim == 3 else (n_idx,)
+
+
+class ResidentHandle:
+    """Owns one ``ffk_resident`` handle: device memory and a pinned host block, filled by a pass and freed with
+    the object.  *shape* is what the last pass left (None: nothing yet)."""
 
     def __init__(self):
         self._lib = _lib.load()
         self._handle = ctypes.c_void_p()
         check(self._lib.ffk_resident_create(ctypes.byref(self._handle)))
         self.shape = None
-        self._filter_function = None      # weak: the array's buffer owns this object, not vice versa
 
     def __del__(self):
         handle, self._handle = getattr(self, '_handle', None), None
@@ -109,6 +118,20 @@ class ResidentResult:
 
     def __reduce__(self):
         return (type(None), ())
+
+    @property
+    def handle(self):
+        """The ``ffk_resident*`` (for calls that read resident control matrices in place)."""
+        return self._handle
+
+
+class ResidentResult(ResidentHandle):
+    """Owns one ``ffk_resident`` handle: the device-resident control matrix, filter function and
+    frequency grid of one pass, and the pinned host block the small results live in."""
+
+    def __init__(self):
+        super().__init__()
+        self._filter_function = None      # weak: the array's buffer owns this object, not vice versa
 
     def evaluate(self, hamiltonian, dt, t, omega, basis, n_opers, n_coeffs, c_coeffs=None,
                  spectrum=None, idx=None, d_infidelity=None):
@@ -130,15 +153,12 @@ class ResidentResult:
             c = as_f64(c_coeffs)
             if c.shape != (len(H), G):
                 raise ValueError(f'Expected c_coeffs of shape ({len(H)}, {G}), not {c.shape}.')
-            idx = np.ascontiguousarray(idx, dtype=np.int32)
-            real = not np.iscomplexobj(spectrum)
-            S = as_f64(spectrum) if real else as_c128(spectrum)
-            n_idx = len(idx)
-            infid = np.empty((n_idx, n_idx) if S.ndim == 3 else (n_idx,), dtype=np.float64)
+            S, real, idx, out_shape = spectrum_arguments(spectrum, idx)
+            infid = np.empty(out_shape, dtype=np.float64)
             check(self._lib.ffk_resident_filter_function_infidelity(
                 self._handle, H.ctypes.data, len(H), c.ctypes.data, dt.ctypes.data, t.ctypes.data, G, d,
                 omega.ctypes.data, W, C.ctypes.data, N, B.ctypes.data, A, s.ctypes.data, S.ctypes.data,
-                S.ndim, int(real), idx.ctypes.data, n_idx, int(d_infidelity), *results, infid.ctypes.data))
+                S.ndim, real, idx.ctypes.data, len(idx), int(d_infidelity), *results, infid.ctypes.data))
         elif c_coeffs is None:
             check(self._lib.ffk_resident_filter_function(
                 self._handle, H.ctypes.data, dt.ctypes.data, t.ctypes.data, G, d, omega.ctypes.data, W,
@@ -171,11 +191,6 @@ class ResidentResult:
         self._filter_function = weakref.ref(filter_function)
 
     @property
-    def handle(self):
-        """The ``ffk_resident*`` (for calls that read several resident results)."""
-        return self._handle
-
-    @property
     def filter_function(self):
         """The host array of the resident F, if it is still alive."""
         return None if self._filter_function is None else self._filter_function()
@@ -203,14 +218,11 @@ class ResidentResult:
         (``util.parse_spectrum``), *idx* the noise-operator indices, *d* the pulse's (possibly
         user-overridden) dimension."""
         G, _, W, N, A = self.shape
-        idx = np.ascontiguousarray(idx, dtype=np.int32)
-        real = not np.iscomplexobj(spectrum)
-        S = as_f64(spectrum) if real else as_c128(spectrum)
-        n_idx = len(idx)
-        out = np.empty((n_idx, n_idx) if S.ndim == 3 else (n_idx,), dtype=np.float64)
+        S, real, idx, out_shape = spectrum_arguments(spectrum, idx)
+        out = np.empty(out_shape, dtype=np.float64)
         if W < 2:
             out[...] = 0.0
             return out
-        check(self._lib.ffk_resident_infidelity(self._handle, S.ctypes.data, S.ndim, int(real),
-                                                idx.ctypes.data, n_idx, int(d), out.ctypes.data))
+        check(self._lib.ffk_resident_infidelity(self._handle, S.ctypes.data, S.ndim, real,
+                                                idx.ctypes.data, len(idx), int(d), out.ctypes.data))
         return out

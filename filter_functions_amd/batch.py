@@ -13,9 +13,9 @@ import functools
 
 import numpy as np
 
-from . import _lib, numeric, util
+from . import numeric, util
 from ._lib import as_c128, as_f64, check
-from ._resident import Deferred, _view
+from ._resident import Deferred, ResidentHandle, _view, spectrum_arguments
 
 __all__ = ['get_filter_functions', 'infidelities']
 
@@ -25,32 +25,10 @@ PASS_BYTES = 1 << 30
 MAX_PULSES = 8192
 
 
-class BatchResult:
+class BatchResult(ResidentHandle):
     """Owns one ``ffk_resident`` handle filled by a batched pass: the device-resident control matrices
     and the pinned host block the per-pulse results live in.  Shared by the members of the pass, freed
     when the last of them lets go."""
-
-    def __init__(self):
-        self._lib = _lib.load()
-        self._handle = ctypes.c_void_p()
-        check(self._lib.ffk_resident_create(ctypes.byref(self._handle)))
-        self.shape = None
-
-    def __del__(self):
-        handle, self._handle = getattr(self, '_handle', None), None
-        if handle:
-            self._lib.ffk_resident_destroy(handle)
-
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (type(None), ())
-
-    @property
-    def handle(self):
-        """The ``ffk_resident*`` (for calls that read the members' control matrices in place)."""
-        return self._handle
 
     def evaluate(self, c_opers, c_coeffs, dt, t, omega, basis, n_opers, n_coeffs, spectrum=None, idx=None,
                  d_infidelity=None):
@@ -67,11 +45,9 @@ class BatchResult:
         infid = S = None
         s_ndim = real = n_idx = 0
         if spectrum is not None:
-            idx = np.ascontiguousarray(idx, dtype=np.int32)
-            real = int(not np.iscomplexobj(spectrum))
-            S = as_f64(spectrum) if real else as_c128(spectrum)
+            S, real, idx, out_shape = spectrum_arguments(spectrum, idx)
             s_ndim, n_idx = S.ndim, len(idx)
-            infid = np.empty((P,) + ((n_idx, n_idx) if S.ndim == 3 else (n_idx,)), dtype=np.float64)
+            infid = np.empty((P,) + out_shape, dtype=np.float64)
         status = self._lib.ffk_resident_batch_filter_function_infidelity(
             self._handle, P, C.ctypes.data, n_c, c.ctypes.data, dt.ctypes.data, t.ctypes.data, G, d,
             omega.ctypes.data, W, basis.ctypes.data, N, B.ctypes.data, A, s.ctypes.data,

@@ -5,8 +5,11 @@
 //   ffk_api.hip           device / stream utilities, diagonalize, control matrix, filter function,
 //                         infidelity, Liouville representation, the fused pipeline pass (SURVEY 8 a)
 //   ffk_api_sequence.hip  concatenation rule, decay amplitudes, cumulant function, expm (SURVEY 8 f)
-//   ffk_api_resident.hip  resident results behind PulseSequence / ff.infidelity; host self test
+//   ffk_api_resident.hip  resident results behind PulseSequence / ff.infidelity, the batched, sequence and
+//                         process passes on resident handles; host self test
 //   ffk_api_frozen.hip    second order and gradient (outside SURVEY 8, frozen since round 2)
+//   ffk_api_batch.hip     many pulses of one shape in one pass of the pipeline (ffk_pipeline_batch_dev)
+//   ffk_api_batch_grad.hip  the gradient of the filter function / infidelity of many pulses in one pass
 #pragma once
 #include <cstdarg>
 #include <cstdio>

@@ -10,8 +10,8 @@
 namespace {
 
 struct Block {
-    void* ptr;
-    size_t size;
+    void* ptr = nullptr;
+    size_t size = 0;
     int device = -1;      // device blocks belong to one device; pinned host blocks are portable
 };
 
@@ -64,6 +64,18 @@ struct BlockPool {
     }
 };
 BlockPool g_dev_pool(false), g_pin_pool(true);
+
+// A pinned block for the duration of one call.  Kernels read and write it as mapped host memory: declare the lease
+// BEFORE the arena lock and the StreamDrain, so that the block goes back to the pool only after the stream has drained.
+struct PinLease {
+    Block block;
+    PinLease() = default;
+    PinLease(const PinLease&) = delete;
+    PinLease& operator=(const PinLease&) = delete;
+    ~PinLease() { g_pin_pool.give(block); }
+    int take(size_t bytes, int device) { return g_pin_pool.take(bytes, device, &block); }
+    unsigned char* ptr() const { return static_cast<unsigned char*>(block.ptr); }
+};
 // one stream per device for the resident passes, created on first use
 std::mutex g_resident_stream_mu;
 hipStream_t g_resident_streams[64] = {};
@@ -112,23 +124,139 @@ ResidentLayout resident_layout(int G, int d, int W, int N, int A) {
     return L;
 }
 
+// The spectrum of an infidelity integral as the kernels read it: `rows` rows of W c128 values (one for all selected
+// noise operators, one each, or one per pair), and the `n_out` integrals it gives per pulse.
+struct SpectrumShape {
+    size_t rows = 0, n_out = 0;
+};
+SpectrumShape spectrum_shape(int s_ndim, int n_idx) {
+    return {s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx),
+            s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx)};
+}
+
+// `others_ok`: what else the entry point asks of its spectrum arguments (an output array, W >= 2)
+int check_spectrum_args(int s_ndim, const int32_t* idx, int n_idx, int A, int d, bool others_ok) {
+    FFK_REQUIRE(idx && s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= A && d >= 1 && others_ok,
+                "bad spectrum arguments");
+    for (int i = 0; i < n_idx; ++i)
+        FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "idx[%d] = %d outside [0, %d)", i, idx[i], A);
+    return FFK_OK;
+}
+
+// the spectrum (n values; a real one widened to c128) and the operator indices into a pinned block
+void stage_spectrum(const double* spectrum, bool is_real, size_t n, const int32_t* idx, int n_idx, void* spectrum_at,
+                    void* idx_at) {
+    double* hs = static_cast<double*>(spectrum_at);
+    if (is_real) {
+        for (size_t i = 0; i < n; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
+    } else {
+        std::memcpy(hs, spectrum, 16*n);
+    }
+    std::memcpy(idx_at, idx, sizeof(int32_t)*size_t(n_idx));
+}
+
 }  // namespace
 
 struct ffk_resident {
     double t_stage = 0, t_enqueue = 0, t_wait = 0;   // seconds, last pass (host clock)
     int device = -1;
-    int G = 0, d = 0, W = 0, N = 0, A = 0;
-    bool valid = false;
-    Block dev = {nullptr, 0, -1}, pin = {nullptr, 0, -1};
-    ResidentLayout L = {};
-    // a batched pass (ffk_resident_batch_filter_function_infidelity) leaves `valid` false: the single-pulse readers
-    // do not apply to it
-    int P = 0;
-    bool batch_valid = false;
-    size_t batch_R = 0;           // device offset of the control matrices (P, A, N, W)
-    size_t batch_F = 0;           // device offsets of the filter functions (P, A, A, W) and of the grid (W)
-    size_t batch_omega = 0;
+    Block dev, pin;
+    // What the blocks hold: nothing, the result of one pulse (a single pass, a concatenation with a result), or the
+    // members of a batched or sequence pass.  The single-pulse readers serve the first kind only, the batched readers
+    // the second only.
+    enum Kind { NOTHING, SINGLE, MEMBERS } kind = NOTHING;
+    int P = 0;                               // members (1: a single result)
+    int d = 0, W = 0, N = 0, A = 0;
+    size_t R = 0, F = 0, omega = 0;          // device offsets: control matrices (P, A, N, W), filter functions
+                                             // (P, A, A, W), the grid (W)
+    // a single result only:
+    size_t total_propagator = 0;             // pinned offset of the pulse's total propagator (d, d)
+    size_t stage_bytes = 0;                  // pinned bytes from offset 0 that are free after the pass (its inputs):
+                                             // where ffk_resident_infidelity stages its spectrum
+
+    void hold(Kind k, int members, int d_, int W_, int N_, int A_, size_t R_, size_t F_, size_t omega_) {
+        kind = k; P = members; d = d_; W = W_; N = N_; A = A_; R = R_; F = F_; omega = omega_;
+    }
 };
+
+namespace {
+
+// Blocks of at least these sizes on `device` for a pass that is about to overwrite the handle: what it held is gone.
+int ensure_blocks(ffk_resident* r, int device, size_t device_bytes, size_t pinned_bytes) {
+    r->kind = ffk_resident::NOTHING;
+    if (r->device == device && r->dev.size >= device_bytes && r->pin.size >= pinned_bytes) return FFK_OK;
+    g_dev_pool.give(r->dev);
+    g_pin_pool.give(r->pin);
+    r->dev = r->pin = Block{};
+    if (int rc = g_dev_pool.take(device_bytes, device, &r->dev)) return rc;
+    if (int rc = g_pin_pool.take(pinned_bytes, device, &r->pin)) return rc;
+    r->device = device;
+    return FFK_OK;
+}
+
+// the three host clocks behind ffk_resident_timing: staging the inputs, enqueueing, waiting for the stream
+struct PassClock {
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    double laps[3] = {0, 0, 0};
+    int n = 0;
+    void lap() {
+        const auto now = std::chrono::steady_clock::now();
+        laps[n++] = std::chrono::duration<double>(now - last).count();
+        last = now;
+    }
+    void store(ffk_resident* r) const { r->t_stage = laps[0]; r->t_enqueue = laps[1]; r->t_wait = laps[2]; }
+};
+
+int on_owning_device(const ffk_resident* r) {
+    int dev = -1;
+    FFK_HIP(hipGetDevice(&dev));
+    FFK_REQUIRE(dev == r->device, "resident result lives on device %d, current device is %d",
+                r->device, dev);
+    return FFK_OK;
+}
+
+// The device address of the (A, N, W) control matrix of member `slot` of `g` (slot < 0: of its single result), after
+// checking that the handle lives on `device`, holds control matrices of that shape (d = 0: of any dimension) and
+// holds that member.  `what` number `k` of the call is named in the message.
+int member_control_matrix(const ffk_resident* g, int slot, int device, int d, int A, int N, int W, const char* what,
+                          int k, const unsigned char** at) {
+    FFK_REQUIRE(g->kind != ffk_resident::NOTHING, "%s %d: no resident result in its handle", what, k);
+    FFK_REQUIRE(g->device == device, "%s %d lives on device %d, not on device %d", what, k, g->device, device);
+    FFK_REQUIRE((d == 0 || g->d == d) && g->A == A && g->N == N && g->W == W,
+                "%s %d: shape (d=%d, A=%d, N=%d, W=%d) differs from the expected (d=%d, A=%d, N=%d, W=%d)", what, k,
+                g->d, g->A, g->N, g->W, d ? d : g->d, A, N, W);
+    if (slot < 0)
+        FFK_REQUIRE(g->kind == ffk_resident::SINGLE, "%s %d: its handle holds no single result", what, k);
+    else
+        FFK_REQUIRE(g->kind == ffk_resident::MEMBERS && slot < g->P, "%s %d: slot %d is no member of its handle", what,
+                    k, slot);
+    *at = static_cast<const unsigned char*>(g->dev.ptr) + g->R + 16*size_t(A)*N*W*size_t(slot < 0 ? 0 : slot);
+    return FFK_OK;
+}
+
+// Where each of n control matrices lies on the device: in its handle (member_control_matrix), or -- no handle -- in a
+// row of the host table that the pass uploads: left NULL here and counted, placed by place_host_rows.
+int locate_control_matrices(ffk_resident* const* handles, const int32_t* slots, int n, int device, int d, int A, int N,
+                            int W, const char* what, std::vector<const unsigned char*>* at, int* n_host) {
+    at->assign(size_t(n), nullptr);
+    *n_host = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!handles[k])
+            ++*n_host;
+        else if (int rc = member_control_matrix(handles[k], slots[k], device, d, A, N, W, what, k, &(*at)[k]))
+            return rc;
+    }
+    return FFK_OK;
+}
+void place_host_rows(std::vector<const unsigned char*>* at, const unsigned char* table, size_t row_bytes) {
+    for (const unsigned char*& p : *at)
+        if (!p) {
+            p = table;
+            table += row_bytes;
+        }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -245,36 +373,26 @@ int resident_pass(ffk_resident* r, const double* hamiltonian, const double* c_op
     FFK_REQUIRE(hamiltonian || (c_opers && c_coeffs && n_c >= 1), "NULL argument");
     FFK_REQUIRE(dt && t && omega && basis && n_opers && n_coeffs, "NULL argument");
     FFK_REQUIRE(eigvals && eigvecs && propagators && filter_function, "NULL output argument");
-    r->valid = false;
+    if (spectrum)
+        if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d_inf, infid && W >= 2)) return rc;
     int dev = 0;
     FFK_HIP(hipGetDevice(&dev));
     const ResidentLayout L = resident_layout(G, d, W, N, A);
     // spectrum (as c128), idx and the integrals live behind the outputs in the pinned block: the kernel
     // reads and writes them there (mapped memory), nothing extra crosses PCIe by copy
-    size_t o_spec = 0, o_idx = 0, o_out = 0, pin_need = L.outputs_end, n_out = 0, s_rows = 0;
+    const SpectrumShape sh = spectrum ? spectrum_shape(s_ndim, n_idx) : SpectrumShape{};
+    size_t o_spec = 0, o_idx = 0, o_out = 0, pin_need = L.outputs_end;
     if (spectrum) {
-        FFK_REQUIRE(idx && infid && s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= A && d_inf >= 1 && W >= 2,
-                    "bad spectrum arguments");
-        s_rows = s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx);
-        n_out = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
         o_spec = align_up(L.outputs_end);
-        o_idx = o_spec + align_up(16*s_rows*W);
+        o_idx = o_spec + align_up(16*sh.rows*W);
         o_out = o_idx + align_up(sizeof(int32_t)*size_t(n_idx));
-        pin_need = o_out + align_up(8*n_out);
+        pin_need = o_out + align_up(8*sh.n_out);
     }
-    if (r->device != dev || r->dev.size < L.end || r->pin.size < pin_need) {
-        g_dev_pool.give(r->dev);
-        g_pin_pool.give(r->pin);
-        r->dev = r->pin = Block{nullptr, 0, -1};
-        if (int rc = g_dev_pool.take(L.end, dev, &r->dev)) return rc;
-        if (int rc = g_pin_pool.take(pin_need, dev, &r->pin)) return rc;
-        r->device = dev;
-    }
-    r->G = G; r->d = d; r->W = W; r->N = N; r->A = A; r->L = L;
+    if (int rc = ensure_blocks(r, dev, L.end, pin_need)) return rc;
     unsigned char* hp = static_cast<unsigned char*>(r->pin.ptr);
     unsigned char* dp = static_cast<unsigned char*>(r->dev.ptr);
     const size_t dd = size_t(d)*d;
-    const auto clock0 = std::chrono::steady_clock::now();
+    PassClock clock;
     // controls travel in the slot of the Hamiltonian they replace (if they fit: always, but for
     // one- or two-segment pulses with many control operators, which are summed here instead)
     const size_t ctrl_opers = 16*size_t(hamiltonian ? 0 : n_c)*dd;
@@ -305,15 +423,7 @@ int resident_pass(ffk_resident* r, const double* hamiltonian, const double* c_op
     std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
     std::memcpy(hp + L.n_opers, n_opers, 16*size_t(A)*dd);
     std::memcpy(hp + L.n_coeffs, n_coeffs, 8*size_t(A)*G);
-    if (spectrum) {
-        double* hs = reinterpret_cast<double*>(hp + o_spec);
-        if (spectrum_is_real) {
-            for (size_t i = 0; i < s_rows*W; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
-        } else {
-            std::memcpy(hs, spectrum, 16*s_rows*W);
-        }
-        std::memcpy(hp + o_idx, idx, sizeof(int32_t)*size_t(n_idx));
-    }
+    if (spectrum) stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp + o_spec, hp + o_idx);
     hipStream_t s;
     if (int rc = resident_stream(&s)) return rc;
     // scratch of the pass from the shared arena (held only for the duration of this call)
@@ -324,7 +434,7 @@ int resident_pass(ffk_resident* r, const double* hamiltonian, const double* c_op
     void* ws;
     if (int rc = arena_reserve(wsb + hsb + iwsb, &ws)) return rc;
     StreamDrain drain{s};      // (the successful path has synchronised already: a no-op then)
-    const auto clock1 = std::chrono::steady_clock::now();
+    clock.lap();
     auto dptr = [dp](size_t off) { return reinterpret_cast<double*>(dp + off); };
     const bool count_on_host = ffk::eigh_fail_count_supported(d) && ffk::use_fused_front(G, d);
     // copies in, kernels, copies out: on `s`, no synchronisation
@@ -426,12 +536,10 @@ int resident_pass(ffk_resident* r, const double* hamiltonian, const double* c_op
     }
     if (!enqueued)
         if (int rc = enqueue()) return rc;
-    const auto clock2 = std::chrono::steady_clock::now();
+    clock.lap();
     FFK_HIP(hipStreamSynchronize(s));
-    const auto clock3 = std::chrono::steady_clock::now();
-    r->t_stage = std::chrono::duration<double>(clock1 - clock0).count();
-    r->t_enqueue = std::chrono::duration<double>(clock2 - clock1).count();
-    r->t_wait = std::chrono::duration<double>(clock3 - clock2).count();
+    clock.lap();
+    clock.store(r);
     const int32_t failed = *reinterpret_cast<const int32_t*>(hp + L.status);
     if (failed != 0)
         return fail(FFK_ENOCONV, "Jacobi eigensolver did not converge for %d segment(s)", int(failed));
@@ -440,8 +548,10 @@ int resident_pass(ffk_resident* r, const double* hamiltonian, const double* c_op
     *eigvecs = reinterpret_cast<double*>(hp + L.V);
     *propagators = reinterpret_cast<double*>(hp + L.Q);
     *filter_function = reinterpret_cast<double*>(hp + L.F);
-    if (spectrum) std::memcpy(infid, hp + o_out, 8*n_out);
-    r->valid = true;
+    if (spectrum) std::memcpy(infid, hp + o_out, 8*sh.n_out);
+    r->hold(ffk_resident::SINGLE, 1, d, W, N, A, L.R, L.F, L.omega);
+    r->total_propagator = L.Q + 16*size_t(G)*dd;
+    r->stage_bytes = L.inputs_end;
     return FFK_OK;
 }
 
@@ -493,20 +603,6 @@ int ffk_resident_timing(ffk_resident* r, double* seconds) {
     return FFK_OK;
 }
 
-namespace {
-int on_owning_device(const ffk_resident* r) {
-    int dev = -1;
-    FFK_HIP(hipGetDevice(&dev));
-    FFK_REQUIRE(dev == r->device, "resident result lives on device %d, current device is %d",
-                r->device, dev);
-    return FFK_OK;
-}
-}  // namespace
-
-}  // extern "C"
-
-
-extern "C" {
 
 // ffk_concatenate_sequence for distinct pulses whose control matrices are still resident (every one
 // evaluated by ffk_resident_filter_function* on the same frequency grid): the table is assembled
@@ -529,23 +625,21 @@ int ffk_concatenate_sequence_resident(ffk_resident* const* pulses, const double*
     FFK_REQUIRE(T >= 1 && T <= 65535 && G >= 1, "empty or oversized axis: T=%d G=%d", T, G);
     FFK_REQUIRE(which == 0 || which == 1, "invalid which=%d", which);
     FFK_REQUIRE(!filter_function || which == 0, "the filter function needs the summed control matrix");
-    for (int k = 0; k < T; ++k) FFK_REQUIRE(pulses[k] && pulses[k]->valid, "pulse %d has no resident result", k);
+    FFK_REQUIRE(pulses[0], "pulse 0 has no resident result");
     const ffk_resident* first = pulses[0];
     const int d = first->d, A = first->A, N = first->N, W = first->W;
+    std::vector<const unsigned char*> tab(T);        // the control matrices are read where they lie
     for (int k = 0; k < T; ++k) {
-        const ffk_resident* r = pulses[k];
-        FFK_REQUIRE(r->d == d && r->A == A && r->N == N && r->W == W && r->device == first->device,
-                    "pulse %d: shape (d=%d, A=%d, N=%d, W=%d) or device differs from pulse 0", k, r->d,
-                    r->A, r->N, r->W);
+        FFK_REQUIRE(pulses[k], "pulse %d has no resident result", k);
+        if (int rc = member_control_matrix(pulses[k], -1, first->device, d, A, N, W, "pulse", k, &tab[k])) return rc;
     }
     for (int g = 0; g < G; ++g)
         FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%d] = %d outside [0, %d)", g, index[g], T);
     if (int rc = on_owning_device(first)) return rc;
     hipStream_t s;
     if (int rc = resident_stream(&s)) return rc;
-    std::lock_guard<std::mutex> lock(g_arena.mu);
     const size_t dd = size_t(d)*d;
-    const size_t nU = 16*size_t(T)*dd, nP = 16*size_t(T)*W, nR1 = 16*size_t(A)*N*W, nI = 4*size_t(G);
+    const size_t nU = 16*size_t(T)*dd, nP = 16*size_t(T)*W, nI = 4*size_t(G);
     const size_t nB = 16*size_t(N)*dd, nT = 8*size_t(T), nX = 8*size_t(T);
     // host staging (propagators | tau | index | basis | pointers to the resident control matrices) in
     // one pinned block, one H2D.  The control matrices are read where they lie (round 3: assembling
@@ -553,73 +647,50 @@ int ffk_concatenate_sequence_resident(ffk_resident* const* pulses, const double*
     const size_t oU = 0, oT = oU + align_up(nU), oI = oT + align_up(nT), oB = oI + align_up(nI);
     const size_t oX = oB + align_up(nB);
     const size_t stage = oX + align_up(nX);
-    Block pin = {nullptr, 0, -1};
-    if (int rc = g_pin_pool.take(stage, first->device, &pin)) return rc;
-    unsigned char* hp = static_cast<unsigned char*>(pin.ptr);
-    for (int k = 0; k < T; ++k) {
-        const ffk_resident* r = pulses[k];
-        const unsigned char* q = static_cast<const unsigned char*>(r->pin.ptr) + r->L.Q + 16*size_t(r->G)*dd;
-        std::memcpy(hp + oU + 16*size_t(k)*dd, q, 16*dd);         // Q[-1]: the pulse's total propagator
-    }
+    PinLease pin;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    if (int rc = pin.take(stage, first->device)) return rc;
+    unsigned char* hp = pin.ptr();
+    for (int k = 0; k < T; ++k)         // the pulses' total propagators
+        std::memcpy(hp + oU + 16*size_t(k)*dd,
+                    static_cast<const unsigned char*>(pulses[k]->pin.ptr) + pulses[k]->total_propagator, 16*dd);
     std::memcpy(hp + oT, tau, nT);
     std::memcpy(hp + oI, index, nI);
     std::memcpy(hp + oB, basis, nB);
-    for (int k = 0; k < T; ++k) {
-        const unsigned char* rk = static_cast<const unsigned char*>(pulses[k]->dev.ptr) + pulses[k]->L.R;
-        std::memcpy(hp + oX + 8*size_t(k), &rk, 8);
-    }
-    (void)nR1;
+    std::memcpy(hp + oX, tab.data(), nX);
     void* base;
-    int rc = arena_reserve(stage + align_up(nP) +
-                           sequence_scratch_bytes(G, d, A, N, W, which, hermitian_basis != 0,
-                                                  filter_function != nullptr), &base);
-    if (rc) { g_pin_pool.give(pin); return rc; }
+    if (int rc = arena_reserve(stage + align_up(nP) +
+                               sequence_scratch_bytes(G, d, A, N, W, which, hermitian_basis != 0,
+                                                      filter_function != nullptr), &base))
+        return rc;
     Bump a(base, g_arena.size);
     unsigned char* dS = a.take<unsigned char>(stage);
     double* dP = a.take<double>(nP/8);
     // a result handle takes the layout of a one-segment pass: R, F and the grid in its device block,
     // (identity, total propagator) where the propagators of a pass sit in its host block
-    ResidentLayout RL = {};
-    double* keep_R = nullptr;
-    double* keep_F = nullptr;
+    const ResidentLayout RL = resident_layout(1, d, W, N, A);
+    double *keep_R = nullptr, *keep_F = nullptr, *omega_copy = nullptr;
     if (result) {
-        result->valid = false;
-        RL = resident_layout(1, d, W, N, A);
-        if (result->device != first->device || result->dev.size < RL.end || result->pin.size < RL.outputs_end) {
-            g_dev_pool.give(result->dev);
-            g_pin_pool.give(result->pin);
-            result->dev = result->pin = Block{nullptr, 0, -1};
-            rc = g_dev_pool.take(RL.end, first->device, &result->dev);
-            if (!rc) rc = g_pin_pool.take(RL.outputs_end, first->device, &result->pin);
-            if (rc) { g_pin_pool.give(pin); return rc; }
-            result->device = first->device;
-        }
-        result->G = 1; result->d = d; result->W = W; result->N = N; result->A = A; result->L = RL;
+        if (int rc = ensure_blocks(result, first->device, RL.end, RL.outputs_end)) return rc;
         unsigned char* rp = static_cast<unsigned char*>(result->dev.ptr);
         keep_R = reinterpret_cast<double*>(rp + RL.R);
         keep_F = reinterpret_cast<double*>(rp + RL.F);
+        omega_copy = reinterpret_cast<double*>(rp + RL.omega);
     }
-    auto run = [&]() -> int {
-        StreamDrain drain{s};
-        FFK_HIP(hipMemcpyAsync(dS, hp, stage, hipMemcpyHostToDevice, s));
-        const double* dOmega = reinterpret_cast<const double*>(
-            static_cast<const unsigned char*>(first->dev.ptr) + first->L.omega);
-        double* omega_copy = result ? reinterpret_cast<double*>(static_cast<unsigned char*>(result->dev.ptr) + RL.omega)
-                                    : nullptr;
-        if (int rc2 = sequence_on_device(reinterpret_cast<const double*>(dS + oU), dP, nullptr,
-                                         reinterpret_cast<const int32_t*>(dS + oI),
-                                         reinterpret_cast<const double*>(dS + oB), hermitian_basis, T, G, d,
-                                         A, N, W, which, a, control_matrix, total_propagator,
-                                         propagators_liouville, filter_function, s, keep_R, keep_F,
-                                         reinterpret_cast<const cplx* const*>(dS + oX),
-                                         reinterpret_cast<const double*>(dS + oT), dOmega, omega_copy))
-            return rc2;
-        FFK_HIP(hipStreamSynchronize(s));
-        return FFK_OK;
-    };
-    rc = run();
-    g_pin_pool.give(pin);
-    if (!rc && result) {
+    StreamDrain drain{s};
+    FFK_HIP(hipMemcpyAsync(dS, hp, stage, hipMemcpyHostToDevice, s));
+    const double* dOmega = reinterpret_cast<const double*>(static_cast<const unsigned char*>(first->dev.ptr) +
+                                                           first->omega);
+    if (int rc = sequence_on_device(reinterpret_cast<const double*>(dS + oU), dP, nullptr,
+                                    reinterpret_cast<const int32_t*>(dS + oI),
+                                    reinterpret_cast<const double*>(dS + oB), hermitian_basis, T, G, d, A, N, W,
+                                    which, a, control_matrix, total_propagator, propagators_liouville,
+                                    filter_function, s, keep_R, keep_F,
+                                    reinterpret_cast<const cplx* const*>(dS + oX),
+                                    reinterpret_cast<const double*>(dS + oT), dOmega, omega_copy))
+        return rc;
+    FFK_HIP(hipStreamSynchronize(s));
+    if (result) {
         double* q = reinterpret_cast<double*>(static_cast<unsigned char*>(result->pin.ptr) + RL.Q);
         for (size_t e = 0; e < dd; ++e) {
             q[2*e] = (e / d == e % d) ? 1.0 : 0.0;
@@ -627,23 +698,76 @@ int ffk_concatenate_sequence_resident(ffk_resident* const* pulses, const double*
         }
         std::memcpy(q + 2*dd, total_propagator, 16*dd);
         result->t_stage = result->t_enqueue = result->t_wait = 0.0;
-        result->valid = true;
+        result->hold(ffk_resident::SINGLE, 1, d, W, N, A, RL.R, RL.F, RL.omega);
+        result->total_propagator = RL.Q + 16*dd;
+        result->stage_bytes = RL.inputs_end;
     }
-    return rc;
+    return FFK_OK;
 }
 
-int ffk_resident_control_matrix(ffk_resident* r, double* control_matrix) {
-    FFK_REQUIRE(r && r->valid, "no resident result");
+namespace {
+// member `slot` (slot < 0: the single result) of the handle's control matrices, copied to the host
+int read_control_matrix(const ffk_resident* r, int slot, double* control_matrix) {
     FFK_REQUIRE(control_matrix, "NULL argument");
+    const unsigned char* at;
+    if (int rc = member_control_matrix(r, slot, r->device, r->d, r->A, r->N, r->W, "member", slot, &at)) return rc;
     if (int rc = on_owning_device(r)) return rc;
     hipStream_t s;
     if (int rc = resident_stream(&s)) return rc;
-    const unsigned char* dp = static_cast<const unsigned char*>(r->dev.ptr);
-    FFK_HIP(hipMemcpyAsync(control_matrix, dp + r->L.R, 16*size_t(r->A)*r->N*r->W,
-                           hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipMemcpyAsync(control_matrix, at, 16*size_t(r->A)*r->N*r->W, hipMemcpyDeviceToHost, s));
     FFK_HIP(hipStreamSynchronize(s));
     return FFK_OK;
 }
+}  // namespace
+
+int ffk_resident_control_matrix(ffk_resident* r, double* control_matrix) {
+    FFK_REQUIRE(r && r->kind == ffk_resident::SINGLE, "no resident result");
+    return read_control_matrix(r, -1, control_matrix);
+}
+
+int ffk_resident_batch_control_matrix(ffk_resident* r, int pulse, double* control_matrix) {
+    FFK_REQUIRE(r && r->kind == ffk_resident::MEMBERS, "no resident batch result");
+    FFK_REQUIRE(pulse >= 0 && pulse < r->P, "pulse %d out of range [0, %d)", pulse, r->P);
+    return read_control_matrix(r, pulse, control_matrix);
+}
+
+namespace {
+
+// the batched pass: [inputs: one H2D][outputs: one D2H] in both blocks, then the control matrices on the device only
+struct BatchLayout {
+    size_t c_opers, c_coeffs, dt, t, omega, basis, n_opers, n_coeffs, S, idx, inputs_end;
+    size_t D, V, Q, F, infid, failed, outputs_end;
+    size_t R, end;
+};
+BatchLayout batch_layout(int P, int n_c, int G, int d, int W, int N, int A, SpectrumShape sh, int n_idx) {
+    BatchLayout L;
+    const size_t dd = size_t(d)*d, PG = size_t(P)*G;
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.c_opers = put(16*size_t(P)*n_c*dd);
+    L.c_coeffs = put(8*size_t(P)*n_c*G);
+    L.dt = put(8*PG);
+    L.t = put(8*size_t(P)*(G + 1));
+    L.omega = put(8*size_t(W));
+    L.basis = put(16*size_t(N)*dd);
+    L.n_opers = put(16*size_t(P)*A*dd);
+    L.n_coeffs = put(8*size_t(P)*A*G);
+    L.S = put(16*sh.rows*W);
+    L.idx = put(sizeof(int32_t)*size_t(n_idx));
+    L.inputs_end = o;
+    L.D = put(8*PG*d);
+    L.V = put(16*PG*dd);
+    L.Q = put(16*size_t(P)*(G + 1)*dd);
+    L.F = put(16*size_t(P)*A*A*W);
+    L.infid = put(8*size_t(P)*sh.n_out);
+    L.failed = put(sizeof(int32_t)*P);
+    L.outputs_end = o;
+    L.R = put(16*size_t(P)*A*N*W);
+    L.end = o;
+    return L;
+}
+
+}  // namespace
 
 int ffk_resident_batch_filter_function_infidelity(ffk_resident* r, int P, const double* c_opers, int n_c,
                                                   const double* c_coeffs, const double* dt, const double* t, int G,
@@ -660,58 +784,26 @@ int ffk_resident_batch_filter_function_infidelity(ffk_resident* r, int P, const 
                 A, G, n_c);
     FFK_REQUIRE(c_opers && c_coeffs && dt && t && omega && basis && n_opers && n_coeffs, "NULL argument");
     FFK_REQUIRE(eigvals && eigvecs && propagators && filter_function && n_failed, "NULL output argument");
-    size_t s_rows = 0, n_out = 0;
-    if (spectrum) {
-        FFK_REQUIRE(idx && infid && s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= A && d_inf >= 1 && W >= 2,
-                    "bad spectrum arguments");
-        s_rows = s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx);
-        n_out = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
-    }
-    r->valid = r->batch_valid = false;
+    if (spectrum)
+        if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d_inf, infid && W >= 2)) return rc;
+    const SpectrumShape sh = spectrum ? spectrum_shape(s_ndim, n_idx) : SpectrumShape{};
     int dev = 0;
     FFK_HIP(hipGetDevice(&dev));
     const size_t dd = size_t(d)*d, PG = size_t(P)*G;
-    // [inputs: one H2D][outputs: one D2H] in both blocks, then the control matrices on the device only
-    size_t o = 0;
-    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
-    const size_t o_cop = put(16*size_t(P)*n_c*dd), o_cc = put(8*size_t(P)*n_c*G), o_dt = put(8*PG),
-                 o_t = put(8*size_t(P)*(G + 1)), o_om = put(8*size_t(W)), o_b = put(16*size_t(N)*dd),
-                 o_no = put(16*size_t(P)*A*dd), o_nc = put(8*size_t(P)*A*G), o_S = put(16*s_rows*W),
-                 o_idx = put(sizeof(int32_t)*size_t(n_idx)), inputs_end = o;
-    const size_t o_D = put(8*PG*d), o_V = put(16*PG*dd), o_Q = put(16*size_t(P)*(G + 1)*dd),
-                 o_F = put(16*size_t(P)*A*A*W), o_inf = put(8*size_t(P)*n_out), o_fail = put(sizeof(int32_t)*P),
-                 outputs_end = o;
-    const size_t o_R = put(16*size_t(P)*A*N*W), dev_end = o;
-    if (r->device != dev || r->dev.size < dev_end || r->pin.size < outputs_end) {
-        g_dev_pool.give(r->dev);
-        g_pin_pool.give(r->pin);
-        r->dev = r->pin = Block{nullptr, 0, -1};
-        if (int rc = g_dev_pool.take(dev_end, dev, &r->dev)) return rc;
-        if (int rc = g_pin_pool.take(outputs_end, dev, &r->pin)) return rc;
-        r->device = dev;
-    }
-    r->P = P; r->G = G; r->d = d; r->W = W; r->N = N; r->A = A; r->batch_R = o_R; r->batch_F = o_F;
-    r->batch_omega = o_om;
+    const BatchLayout L = batch_layout(P, n_c, G, d, W, N, A, sh, n_idx);
+    if (int rc = ensure_blocks(r, dev, L.end, L.outputs_end)) return rc;
     unsigned char* hp = static_cast<unsigned char*>(r->pin.ptr);
     unsigned char* dp = static_cast<unsigned char*>(r->dev.ptr);
-    const auto clock0 = std::chrono::steady_clock::now();
-    std::memcpy(hp + o_cop, c_opers, 16*size_t(P)*n_c*dd);
-    std::memcpy(hp + o_cc, c_coeffs, 8*size_t(P)*n_c*G);
-    std::memcpy(hp + o_dt, dt, 8*PG);
-    std::memcpy(hp + o_t, t, 8*size_t(P)*(G + 1));
-    std::memcpy(hp + o_om, omega, 8*size_t(W));
-    std::memcpy(hp + o_b, basis, 16*size_t(N)*dd);
-    std::memcpy(hp + o_no, n_opers, 16*size_t(P)*A*dd);
-    std::memcpy(hp + o_nc, n_coeffs, 8*size_t(P)*A*G);
-    if (spectrum) {
-        double* hs = reinterpret_cast<double*>(hp + o_S);
-        if (spectrum_is_real) {
-            for (size_t i = 0; i < s_rows*W; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
-        } else {
-            std::memcpy(hs, spectrum, 16*s_rows*W);
-        }
-        std::memcpy(hp + o_idx, idx, sizeof(int32_t)*size_t(n_idx));
-    }
+    PassClock clock;
+    std::memcpy(hp + L.c_opers, c_opers, 16*size_t(P)*n_c*dd);
+    std::memcpy(hp + L.c_coeffs, c_coeffs, 8*size_t(P)*n_c*G);
+    std::memcpy(hp + L.dt, dt, 8*PG);
+    std::memcpy(hp + L.t, t, 8*size_t(P)*(G + 1));
+    std::memcpy(hp + L.omega, omega, 8*size_t(W));
+    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
+    std::memcpy(hp + L.n_opers, n_opers, 16*size_t(P)*A*dd);
+    std::memcpy(hp + L.n_coeffs, n_coeffs, 8*size_t(P)*A*G);
+    if (spectrum) stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp + L.S, hp + L.idx);
     hipStream_t s;
     if (int rc = resident_stream(&s)) return rc;
     std::lock_guard<std::mutex> lock(g_arena.mu);
@@ -719,122 +811,90 @@ int ffk_resident_batch_filter_function_infidelity(ffk_resident* r, int P, const 
     void* ws;
     if (int rc = arena_reserve(wsb, &ws)) return rc;
     StreamDrain drain{s};
-    const auto clock1 = std::chrono::steady_clock::now();
+    clock.lap();
     auto dptr = [dp](size_t off) { return reinterpret_cast<double*>(dp + off); };
-    FFK_HIP(hipMemcpyAsync(dp, hp, inputs_end, hipMemcpyHostToDevice, s));
-    if (int rc = pipeline_batch_dev_impl(P, dptr(o_cop), n_c, dptr(o_cc), dptr(o_dt), dptr(o_t), G, d, dptr(o_om), W,
-                                         dptr(o_b), N, dptr(o_no), A, dptr(o_nc), spectrum ? dptr(o_S) : nullptr,
-                                         s_ndim, reinterpret_cast<const int32_t*>(dp + o_idx), n_idx, d_inf,
-                                         dptr(o_D), dptr(o_V), dptr(o_Q), dptr(o_R), dptr(o_F),
-                                         spectrum ? dptr(o_inf) : nullptr, ws, wsb, s))
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    if (int rc = pipeline_batch_dev_impl(P, dptr(L.c_opers), n_c, dptr(L.c_coeffs), dptr(L.dt), dptr(L.t), G, d,
+                                         dptr(L.omega), W, dptr(L.basis), N, dptr(L.n_opers), A, dptr(L.n_coeffs),
+                                         spectrum ? dptr(L.S) : nullptr, s_ndim,
+                                         reinterpret_cast<const int32_t*>(dp + L.idx), n_idx, d_inf, dptr(L.D),
+                                         dptr(L.V), dptr(L.Q), dptr(L.R), dptr(L.F),
+                                         spectrum ? dptr(L.infid) : nullptr, ws, wsb, s))
         return rc;
-    if (int rc = ffk_eigensolver_status_batch_dev(ws, wsb, P, G, d, reinterpret_cast<int32_t*>(dp + o_fail), s))
+    if (int rc = ffk_eigensolver_status_batch_dev(ws, wsb, P, G, d, reinterpret_cast<int32_t*>(dp + L.failed), s))
         return rc;
-    FFK_HIP(hipMemcpyAsync(hp + o_D, dp + o_D, outputs_end - o_D, hipMemcpyDeviceToHost, s));
-    const auto clock2 = std::chrono::steady_clock::now();
+    FFK_HIP(hipMemcpyAsync(hp + L.D, dp + L.D, L.outputs_end - L.D, hipMemcpyDeviceToHost, s));
+    clock.lap();
     FFK_HIP(hipStreamSynchronize(s));
-    const auto clock3 = std::chrono::steady_clock::now();
-    r->t_stage = std::chrono::duration<double>(clock1 - clock0).count();
-    r->t_enqueue = std::chrono::duration<double>(clock2 - clock1).count();
-    r->t_wait = std::chrono::duration<double>(clock3 - clock2).count();
+    clock.lap();
+    clock.store(r);
     if (int rc = kernel_fault_status()) return rc;
-    std::memcpy(n_failed, hp + o_fail, sizeof(int32_t)*P);
+    std::memcpy(n_failed, hp + L.failed, sizeof(int32_t)*P);
     for (int p = 0; p < P; ++p)
         if (n_failed[p] != 0)
             return fail(FFK_ENOCONV, "Jacobi eigensolver did not converge for %d segment(s) of pulse %d of the batch",
                         int(n_failed[p]), p);
-    *eigvals = reinterpret_cast<double*>(hp + o_D);
-    *eigvecs = reinterpret_cast<double*>(hp + o_V);
-    *propagators = reinterpret_cast<double*>(hp + o_Q);
-    *filter_function = reinterpret_cast<double*>(hp + o_F);
-    if (spectrum) std::memcpy(infid, hp + o_inf, 8*size_t(P)*n_out);
-    r->batch_valid = true;
-    return FFK_OK;
-}
-
-int ffk_resident_batch_control_matrix(ffk_resident* r, int pulse, double* control_matrix) {
-    FFK_REQUIRE(r && r->batch_valid, "no resident batch result");
-    FFK_REQUIRE(control_matrix, "NULL argument");
-    FFK_REQUIRE(pulse >= 0 && pulse < r->P, "pulse %d out of range [0, %d)", pulse, r->P);
-    if (int rc = on_owning_device(r)) return rc;
-    hipStream_t s;
-    if (int rc = resident_stream(&s)) return rc;
-    const size_t bytes = 16*size_t(r->A)*r->N*r->W;
-    const unsigned char* dp = static_cast<const unsigned char*>(r->dev.ptr);
-    FFK_HIP(hipMemcpyAsync(control_matrix, dp + r->batch_R + size_t(pulse)*bytes, bytes, hipMemcpyDeviceToHost, s));
-    FFK_HIP(hipStreamSynchronize(s));
+    *eigvals = reinterpret_cast<double*>(hp + L.D);
+    *eigvecs = reinterpret_cast<double*>(hp + L.V);
+    *propagators = reinterpret_cast<double*>(hp + L.Q);
+    *filter_function = reinterpret_cast<double*>(hp + L.F);
+    if (spectrum) std::memcpy(infid, hp + L.infid, 8*size_t(P)*sh.n_out);
+    r->hold(ffk_resident::MEMBERS, P, d, W, N, A, L.R, L.F, L.omega);
     return FFK_OK;
 }
 
 int ffk_resident_control_matrix_dev(ffk_resident* r, const double** control_matrix,
                                     const double** filter_function, const double** omega) {
-    FFK_REQUIRE(r && r->valid, "no resident result");
+    FFK_REQUIRE(r && r->kind == ffk_resident::SINGLE, "no resident result");
     const unsigned char* dp = static_cast<const unsigned char*>(r->dev.ptr);
-    if (control_matrix) *control_matrix = reinterpret_cast<const double*>(dp + r->L.R);
-    if (filter_function) *filter_function = reinterpret_cast<const double*>(dp + r->L.F);
-    if (omega) *omega = reinterpret_cast<const double*>(dp + r->L.omega);
+    if (control_matrix) *control_matrix = reinterpret_cast<const double*>(dp + r->R);
+    if (filter_function) *filter_function = reinterpret_cast<const double*>(dp + r->F);
+    if (omega) *omega = reinterpret_cast<const double*>(dp + r->omega);
     return FFK_OK;
 }
 
 int ffk_resident_infidelity(ffk_resident* r, const double* spectrum, int s_ndim, int spectrum_is_real,
                             const int32_t* idx, int n_idx, int d, double* infid) {
-    FFK_REQUIRE(r && r->valid, "no resident result");
+    FFK_REQUIRE(r && r->kind == ffk_resident::SINGLE, "no resident result");
     FFK_REQUIRE(spectrum && idx && infid, "NULL argument");
-    FFK_REQUIRE(s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= r->A && d >= 1, "bad spectrum arguments");
+    if (int rc = check_spectrum_args(s_ndim, idx, n_idx, r->A, d, true)) return rc;
     if (int rc = on_owning_device(r)) return rc;
     const int W = r->W, A = r->A;
-    const size_t rows = s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx);
-    const size_t n_out = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
-    unsigned char* hp = static_cast<unsigned char*>(r->pin.ptr);
+    const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
     unsigned char* dp = static_cast<unsigned char*>(r->dev.ptr);
-    const ResidentLayout& L = r->L;
     // stage spectrum (as c128), idx and the result in the pinned input region (free after the pass).
     // Round 3: the kernel reads spectrum and idx FROM that pinned block and writes the integrals INTO
     // it (pinned host memory is mapped into the device's address space): one launch and one
     // synchronisation instead of two H2D copies, the launch, a D2H copy into pageable memory and
     // the synchronisation -- the spectrum is read once (64 KB over PCIe at config 2)
-    const size_t s_bytes = 16*rows*W;
-    const size_t o_idx = align_up(s_bytes), o_out = o_idx + align_up(sizeof(int32_t)*size_t(n_idx));
-    const size_t stage = o_out + align_up(8*n_out);
+    const size_t o_idx = align_up(16*sh.rows*W), o_out = o_idx + align_up(sizeof(int32_t)*size_t(n_idx));
+    const size_t stage = o_out + align_up(8*sh.n_out);
     hipStream_t s;
     if (int rc = resident_stream(&s)) return rc;
-    const bool fits = stage <= L.inputs_end;
-    Block extra = {nullptr, 0, -1};
-    unsigned char* stage_ptr = hp;
-    if (!fits) {
-        if (int rc = g_pin_pool.take(stage, r->device, &extra)) return rc;
-        stage_ptr = static_cast<unsigned char*>(extra.ptr);
+    PinLease extra;                    // a spectrum larger than the pass's inputs gets a block of its own
+    unsigned char* stage_ptr = static_cast<unsigned char*>(r->pin.ptr);
+    if (stage > r->stage_bytes) {
+        if (int rc = extra.take(stage, r->device)) return rc;
+        stage_ptr = extra.ptr();
     }
-    double* hs = reinterpret_cast<double*>(stage_ptr);
-    if (spectrum_is_real) {
-        for (size_t i = 0; i < rows*W; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
-    } else {
-        std::memcpy(hs, spectrum, s_bytes);
-    }
-    std::memcpy(stage_ptr + o_idx, idx, sizeof(int32_t)*size_t(n_idx));
-    int rc = FFK_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_arena.mu);
-        const size_t iwsb = ffk_infidelity_workspace_bytes(W, n_idx, s_ndim);
-        void* iws;
-        rc = arena_reserve(iwsb, &iws);
-        if (!rc) {
-            PassOptions opt;
-            opt.infid_spectrum_on_host = true;
-            rc = infidelity_dev_impl(reinterpret_cast<const double*>(dp + L.F), A, W,
+    stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, stage_ptr, stage_ptr + o_idx);
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    const size_t iwsb = ffk_infidelity_workspace_bytes(W, n_idx, s_ndim);
+    void* iws;
+    if (int rc = arena_reserve(iwsb, &iws)) return rc;
+    StreamDrain drain{s};
+    PassOptions opt;
+    opt.infid_spectrum_on_host = true;
+    if (int rc = infidelity_dev_impl(reinterpret_cast<const double*>(dp + r->F), A, W,
                                      reinterpret_cast<const double*>(stage_ptr), s_ndim,
-                                     reinterpret_cast<const double*>(dp + L.omega),
+                                     reinterpret_cast<const double*>(dp + r->omega),
                                      reinterpret_cast<const int32_t*>(stage_ptr + o_idx), n_idx, d,
-                                     reinterpret_cast<double*>(stage_ptr + o_out), iws, iwsb, s, opt);
-        }
-        if (!rc) {
-            const hipError_t e = hipStreamSynchronize(s);
-            if (e != hipSuccess) rc = fail(FFK_EHIP, "infidelity failed: %s", hipGetErrorString(e));
-            else std::memcpy(infid, stage_ptr + o_out, 8*n_out);
-        }
-    }
-    g_pin_pool.give(extra);
-    return rc;
+                                     reinterpret_cast<double*>(stage_ptr + o_out), iws, iwsb, s, opt))
+        return rc;
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(FFK_EHIP, "infidelity failed: %s", hipGetErrorString(e));
+    std::memcpy(infid, stage_ptr + o_out, 8*sh.n_out);
+    return FFK_OK;
 }
 
 // ---- many sequences from one gate table in ONE pass (ff.concatenate_sequences; sequences.hip) ----------------
@@ -846,8 +906,7 @@ struct SeqLayout {
     size_t R, phases, L, end;                                                           // device only
 };
 
-SeqLayout seq_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W, size_t s_rows, int n_idx,
-                     size_t n_out) {
+SeqLayout seq_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W, SpectrumShape sh, int n_idx) {
     SeqLayout L;
     const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
     size_t o = 0;
@@ -861,22 +920,18 @@ SeqLayout seq_layout(int T, int P, size_t n_index, int n_host, int d, int A, int
     L.U = put(16*size_t(T)*dd);
     L.tab = put(8*size_t(T));
     L.host = put(row*size_t(n_host));
-    L.S = put(16*s_rows*W);
+    L.S = put(16*sh.rows*W);
     L.idx = put(4*size_t(n_idx));
     L.inputs_end = o;
     L.Q = put(16*size_t(P)*dd);
     L.F = put(16*size_t(P)*A*A*W);
-    L.infid = put(8*size_t(P)*n_out);
+    L.infid = put(8*size_t(P)*sh.n_out);
     L.outputs_end = o;
     L.R = put(row*size_t(P));
     L.phases = put(16*size_t(T)*W);
     L.L = put(8*size_t(T)*N*N);
     L.end = o;
     return L;
-}
-
-size_t spectrum_rows(int s_ndim, int n_idx) {
-    return s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx);
 }
 
 }  // namespace
@@ -886,9 +941,8 @@ size_t ffk_concatenate_sequences_workspace_bytes(int T, int P, int n_index, int 
     if (T < 1 || P < 1 || n_index < P || n_host < 0 || n_host > T || !ffk::sequences_supported(d, N, A) || W < 1)
         return 0;
     if (s_ndim != 0 && (s_ndim < 1 || s_ndim > 3 || n_idx < 1 || n_idx > A)) return 0;
-    const size_t n_out = s_ndim == 0 ? 0 : (s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx));
-    return seq_layout(T, P, size_t(n_index), n_host, d, A, N, W, s_ndim ? spectrum_rows(s_ndim, n_idx) : 0,
-                      s_ndim ? n_idx : 0, n_out).end;
+    return seq_layout(T, P, size_t(n_index), n_host, d, A, N, W,
+                      s_ndim ? spectrum_shape(s_ndim, n_idx) : SpectrumShape{}, s_ndim ? n_idx : 0).end;
 }
 
 int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const* gates, const int32_t* slots,
@@ -913,50 +967,27 @@ int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const
     const size_t n_index = size_t(offsets[P]);
     for (size_t g = 0; g < n_index; ++g)
         FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
-    size_t s_rows = 0, n_out = 0;
     if (spectrum) {
-        FFK_REQUIRE(idx && infid && s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= A && d_infidelity >= 1 &&
-                    W >= 2, "bad spectrum arguments");
-        for (int i = 0; i < n_idx; ++i) FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "idx[%d] = %d outside [0, %d)", i, idx[i], A);
-        s_rows = spectrum_rows(s_ndim, n_idx);
-        n_out = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
+        if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d_infidelity, infid && W >= 2)) return rc;
     } else {
         n_idx = 0;
     }
+    const SpectrumShape sh = spectrum ? spectrum_shape(s_ndim, n_idx) : SpectrumShape{};
     int dev = 0;
     FFK_HIP(hipGetDevice(&dev));
+    for (int k = 0; k < T; ++k)
+        FFK_REQUIRE(gates[k] != result, "gate %d: the result handle must not be an input", k);
+    // where each gate's control matrix lies on the device: in its own handle, or in the uploaded host table
+    std::vector<const unsigned char*> tab;
     int n_host = 0;
-    for (int k = 0; k < T; ++k) {
-        const ffk_resident* g = gates[k];
-        if (!g) {
-            ++n_host;
-            continue;
-        }
-        FFK_REQUIRE(g != result, "gate %d: the result handle must not be an input", k);
-        FFK_REQUIRE(g->device == dev, "gate %d lives on device %d, current device is %d", k, g->device, dev);
-        FFK_REQUIRE(g->d == d && g->A == A && g->N == N && g->W == W,
-                    "gate %d: shape (d=%d, A=%d, N=%d, W=%d) differs from the pass's (d=%d, A=%d, N=%d, W=%d)", k,
-                    g->d, g->A, g->N, g->W, d, A, N, W);
-        if (slots[k] < 0)
-            FFK_REQUIRE(g->valid, "gate %d: no resident result in its handle", k);
-        else
-            FFK_REQUIRE(g->batch_valid && slots[k] < g->P, "gate %d: slot %d is no member of its handle", k, slots[k]);
-    }
+    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
     FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
-    const SeqLayout L = seq_layout(T, P, n_index, n_host, d, A, N, W, s_rows, n_idx, n_out);
-    result->valid = result->batch_valid = false;
-    if (result->device != dev || result->dev.size < L.end || result->pin.size < L.outputs_end) {
-        g_dev_pool.give(result->dev);
-        g_pin_pool.give(result->pin);
-        result->dev = result->pin = Block{nullptr, 0, -1};
-        if (int rc = g_dev_pool.take(L.end, dev, &result->dev)) return rc;
-        if (int rc = g_pin_pool.take(L.outputs_end, dev, &result->pin)) return rc;
-        result->device = dev;
-    }
+    const SeqLayout L = seq_layout(T, P, n_index, n_host, d, A, N, W, sh, n_idx);
+    if (int rc = ensure_blocks(result, dev, L.end, L.outputs_end)) return rc;
     unsigned char* hp = static_cast<unsigned char*>(result->pin.ptr);
     unsigned char* dp = static_cast<unsigned char*>(result->dev.ptr);
     const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
-    const auto clock0 = std::chrono::steady_clock::now();
+    PassClock clock;
     // the sequences sorted by length, longest first (stable): the rule kernel deals them out in this order
     std::vector<int32_t> order(P);
     for (int p = 0; p < P; ++p) order[p] = p;
@@ -970,33 +1001,14 @@ int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const
     std::memcpy(hp + L.omega, omega, 8*size_t(W));
     std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
     std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
-    // where each gate's control matrix lies on the device: in its own handle, or in the uploaded host table
-    int host_row = 0;
-    for (int k = 0; k < T; ++k) {
-        const ffk_resident* g = gates[k];
-        const unsigned char* at;
-        if (!g)
-            at = dp + L.host + row*size_t(host_row++);
-        else if (slots[k] < 0)
-            at = static_cast<const unsigned char*>(g->dev.ptr) + g->L.R;
-        else
-            at = static_cast<const unsigned char*>(g->dev.ptr) + g->batch_R + row*size_t(slots[k]);
-        std::memcpy(hp + L.tab + 8*size_t(k), &at, 8);
-    }
+    place_host_rows(&tab, dp + L.host, row);
+    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
     if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
-    if (spectrum) {
-        double* hs = reinterpret_cast<double*>(hp + L.S);
-        if (spectrum_is_real) {
-            for (size_t i = 0; i < s_rows*W; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
-        } else {
-            std::memcpy(hs, spectrum, 16*s_rows*W);
-        }
-        std::memcpy(hp + L.idx, idx, 4*size_t(n_idx));
-    }
+    if (spectrum) stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp + L.S, hp + L.idx);
     hipStream_t s;
     if (int rc = resident_stream(&s)) return rc;
     StreamDrain drain{s};
-    const auto clock1 = std::chrono::steady_clock::now();
+    clock.lap();
     auto at = [dp](size_t off) { return dp + off; };
     FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
     const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
@@ -1017,21 +1029,15 @@ int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const
                                               reinterpret_cast<const int32_t*>(at(L.idx)), n_idx, d_infidelity,
                                               reinterpret_cast<double*>(at(L.infid)), s));
     FFK_HIP(hipMemcpyAsync(hp + L.Q, dp + L.Q, L.outputs_end - L.Q, hipMemcpyDeviceToHost, s));
-    const auto clock2 = std::chrono::steady_clock::now();
+    clock.lap();
     FFK_HIP(hipStreamSynchronize(s));
-    const auto clock3 = std::chrono::steady_clock::now();
-    result->t_stage = std::chrono::duration<double>(clock1 - clock0).count();
-    result->t_enqueue = std::chrono::duration<double>(clock2 - clock1).count();
-    result->t_wait = std::chrono::duration<double>(clock3 - clock2).count();
+    clock.lap();
+    clock.store(result);
     if (int rc = kernel_fault_status()) return rc;
     std::memcpy(total_propagators, hp + L.Q, 16*size_t(P)*dd);
     *filter_function = reinterpret_cast<double*>(hp + L.F);
-    if (spectrum) std::memcpy(infid, hp + L.infid, 8*size_t(P)*n_out);
-    result->P = P; result->G = 1; result->d = d; result->W = W; result->N = N; result->A = A;
-    result->batch_R = L.R;
-    result->batch_F = L.F;
-    result->batch_omega = L.omega;
-    result->batch_valid = true;
+    if (spectrum) std::memcpy(infid, hp + L.infid, 8*size_t(P)*sh.n_out);
+    result->hold(ffk_resident::MEMBERS, P, d, W, N, A, L.R, L.F, L.omega);
     return FFK_OK;
 }
 
@@ -1041,73 +1047,56 @@ int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const
 int ffk_resident_batch_infidelity(ffk_resident* r, const int32_t* members, int n_members, const double* spectrum,
                                   int s_ndim, int spectrum_is_real, const int32_t* idx, int n_idx, int d,
                                   double* infid) {
-    FFK_REQUIRE(r && r->batch_valid, "no resident batch result");
+    FFK_REQUIRE(r && r->kind == ffk_resident::MEMBERS, "no resident batch result");
     FFK_REQUIRE(members && spectrum && idx && infid, "NULL argument");
     FFK_REQUIRE(n_members >= 1 && n_members <= 65535, "need 1 <= n_members <= 65535, got %d", n_members);
-    FFK_REQUIRE(s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= r->A && d >= 1 && r->W >= 2,
-                "bad spectrum arguments");
-    for (int i = 0; i < n_idx; ++i) FFK_REQUIRE(idx[i] >= 0 && idx[i] < r->A, "idx[%d] = %d outside [0, %d)", i, idx[i], r->A);
+    if (int rc = check_spectrum_args(s_ndim, idx, n_idx, r->A, d, r->W >= 2)) return rc;
     for (int m = 0; m < n_members; ++m)
         FFK_REQUIRE(members[m] >= 0 && members[m] < r->P, "members[%d] = %d outside [0, %d)", m, members[m], r->P);
     if (int rc = on_owning_device(r)) return rc;
     const int W = r->W, A = r->A;
-    const size_t rows = spectrum_rows(s_ndim, n_idx);
-    const size_t n_out = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
-    const size_t fbytes = 16*size_t(A)*A*W;
+    const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
+    const size_t fbytes = 16*size_t(A)*A*W, out_bytes = 8*size_t(n_members)*sh.n_out;
     bool consecutive = true;
     for (int m = 1; m < n_members; ++m) consecutive = consecutive && members[m] == members[m - 1] + 1;
-    const size_t o_idx = align_up(16*rows*W), o_out = o_idx + align_up(4*size_t(n_idx));
-    const size_t stage = o_out + align_up(8*size_t(n_members)*n_out);
-    Block pin = {nullptr, 0, -1};
-    if (int rc = g_pin_pool.take(stage, r->device, &pin)) return rc;
-    unsigned char* hp = static_cast<unsigned char*>(pin.ptr);
-    double* hs = reinterpret_cast<double*>(hp);
-    if (spectrum_is_real) {
-        for (size_t i = 0; i < rows*W; ++i) { hs[2*i] = spectrum[i]; hs[2*i + 1] = 0.0; }
-    } else {
-        std::memcpy(hs, spectrum, 16*rows*W);
-    }
-    std::memcpy(hp + o_idx, idx, 4*size_t(n_idx));
+    const size_t o_idx = align_up(16*sh.rows*W), o_out = o_idx + align_up(4*size_t(n_idx));
+    const size_t stage = o_out + align_up(out_bytes);
+    PinLease pin;
+    if (int rc = pin.take(stage, r->device)) return rc;
+    unsigned char* hp = pin.ptr();
+    stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp, hp + o_idx);
     hipStream_t s;
-    int rc = resident_stream(&s);
-    if (!rc) {
-        std::lock_guard<std::mutex> lock(g_arena.mu);
-        void* base = nullptr;
-        rc = arena_reserve(stage + (consecutive ? 0 : align_up(fbytes*n_members)), &base);
-        if (!rc) {
-            auto run = [&]() -> int {
-                StreamDrain drain{s};
-                unsigned char* ws = static_cast<unsigned char*>(base);
-                const unsigned char* dp = static_cast<const unsigned char*>(r->dev.ptr);
-                FFK_HIP(hipMemcpyAsync(ws, hp, o_out, hipMemcpyHostToDevice, s));
-                const unsigned char* F = dp + r->batch_F + fbytes*size_t(members[0]);
-                if (!consecutive) {
-                    unsigned char* gathered = ws + stage;
-                    for (int m = 0; m < n_members;) {
-                        int e = m + 1;
-                        while (e < n_members && members[e] == members[e - 1] + 1) ++e;
-                        FFK_HIP(hipMemcpyAsync(gathered + fbytes*size_t(m), dp + r->batch_F + fbytes*size_t(members[m]),
-                                               fbytes*size_t(e - m), hipMemcpyDeviceToDevice, s));
-                        m = e;
-                    }
-                    F = gathered;
-                }
-                FFK_HIP(ffk::launch_infidelity_pulses(reinterpret_cast<const cplx*>(F), A, W, n_members,
-                                                      reinterpret_cast<const cplx*>(ws), s_ndim,
-                                                      reinterpret_cast<const double*>(dp + r->batch_omega),
-                                                      reinterpret_cast<const int32_t*>(ws + o_idx), n_idx, d,
-                                                      reinterpret_cast<double*>(ws + o_out), s));
-                FFK_HIP(hipMemcpyAsync(hp + o_out, ws + o_out, 8*size_t(n_members)*n_out, hipMemcpyDeviceToHost, s));
-                FFK_HIP(hipStreamSynchronize(s));
-                return FFK_OK;
-            };
-            rc = run();
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    void* base = nullptr;
+    if (int rc = arena_reserve(stage + (consecutive ? 0 : align_up(fbytes*n_members)), &base)) return rc;
+    StreamDrain drain{s};
+    unsigned char* ws = static_cast<unsigned char*>(base);
+    const unsigned char* dF = static_cast<const unsigned char*>(r->dev.ptr) + r->F;
+    FFK_HIP(hipMemcpyAsync(ws, hp, o_out, hipMemcpyHostToDevice, s));
+    const unsigned char* F = dF + fbytes*size_t(members[0]);
+    if (!consecutive) {
+        unsigned char* gathered = ws + stage;
+        for (int m = 0; m < n_members;) {
+            int e = m + 1;
+            while (e < n_members && members[e] == members[e - 1] + 1) ++e;
+            FFK_HIP(hipMemcpyAsync(gathered + fbytes*size_t(m), dF + fbytes*size_t(members[m]), fbytes*size_t(e - m),
+                                   hipMemcpyDeviceToDevice, s));
+            m = e;
         }
+        F = gathered;
     }
-    if (!rc) rc = kernel_fault_status();
-    if (!rc) std::memcpy(infid, hp + o_out, 8*size_t(n_members)*n_out);
-    g_pin_pool.give(pin);
-    return rc;
+    FFK_HIP(ffk::launch_infidelity_pulses(reinterpret_cast<const cplx*>(F), A, W, n_members,
+                                          reinterpret_cast<const cplx*>(ws), s_ndim,
+                                          reinterpret_cast<const double*>(static_cast<const unsigned char*>(r->dev.ptr) +
+                                                                          r->omega),
+                                          reinterpret_cast<const int32_t*>(ws + o_idx), n_idx, d,
+                                          reinterpret_cast<double*>(ws + o_out), s));
+    FFK_HIP(hipMemcpyAsync(hp + o_out, ws + o_out, out_bytes, hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    if (int rc = kernel_fault_status()) return rc;
+    std::memcpy(infid, hp + o_out, out_bytes);
+    return FFK_OK;
 }
 
 // ---- decay amplitudes, cumulant functions and error transfer matrices of many pulses in ONE pass, their control
@@ -1127,8 +1116,8 @@ ProcLayout proc_layout(int P, int n_host, int A, int N, int W, int d, int n_idx,
                        bool want_gamma, bool want_K, bool want_U) {
     ProcLayout L;
     const size_t dd = size_t(d)*d, nn = size_t(N)*N;
-    const size_t pairs = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
-    const size_t s_rows = spectrum_rows(s_ndim, n_idx);
+    const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
+    const size_t pairs = sh.n_out, s_rows = sh.rows;
     const int stage = want_U ? 3 : (want_K ? 2 : 1);
     size_t o = 0;
     auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
@@ -1181,8 +1170,9 @@ int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slo
                 "unsupported shape P=%d A=%d N=%d W=%d d=%d n_idx=%d s_ndim=%d (need 1 <= P <= 65535, N <= 16, "
                 "N <= d^2, 1 <= n_idx <= A, 1 <= s_ndim <= 3)", P, A, N, W, d, n_idx, s_ndim);
     FFK_REQUIRE(!single_qubit || (d == 2 && N == 4), "single-qubit expression needs d = 2, N = 4");
-    for (int i = 0; i < n_idx; ++i) FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "idx[%d] = %d outside [0, %d)", i, idx[i], A);
-    const size_t pairs = s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx);
+    if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d, true)) return rc;
+    const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
+    const size_t pairs = sh.n_out, s_rows = sh.rows;
     const bool want_gamma = decay_amplitudes != nullptr, want_K = cumulant_function != nullptr;
     const bool want_U = error_transfer_matrix != nullptr;
     const int stage = want_U ? 3 : (want_K ? 2 : 1);
@@ -1190,92 +1180,63 @@ int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slo
                 "%d pulses of %zu operator pairs exceed the 65535 cumulant functions of one launch", P, pairs);
     int dev = 0;
     FFK_HIP(hipGetDevice(&dev));
+    // where each pulse's control matrix lies on the device: in its handle (of any dimension: only the shape of the
+    // control matrix matters here), or in the uploaded host table
+    std::vector<const unsigned char*> tab;
     int n_host = 0;
-    for (int p = 0; p < P; ++p) {
-        const ffk_resident* g = pulses[p];
-        if (!g) {
-            ++n_host;
-            continue;
-        }
-        FFK_REQUIRE(g->device == dev, "pulse %d lives on device %d, current device is %d", p, g->device, dev);
-        FFK_REQUIRE(g->A == A && g->N == N && g->W == W,
-                    "pulse %d: shape (A=%d, N=%d, W=%d) differs from the pass's (A=%d, N=%d, W=%d)", p, g->A, g->N,
-                    g->W, A, N, W);
-        if (slots[p] < 0)
-            FFK_REQUIRE(g->valid, "pulse %d: no resident result in its handle", p);
-        else
-            FFK_REQUIRE(g->batch_valid && slots[p] < g->P, "pulse %d: slot %d is no member of its handle", p, slots[p]);
-    }
+    if (int rc = locate_control_matrices(pulses, slots, P, dev, 0, A, N, W, "pulse", &tab, &n_host)) return rc;
     FFK_REQUIRE(n_host == 0 || control_matrices, "control_matrices is NULL but %d pulse(s) have no handle", n_host);
     const ProcLayout L = proc_layout(P, n_host, A, N, W, d, n_idx, s_ndim, single_qubit != 0, want_gamma, want_K,
                                      want_U);
-    const size_t s_rows = spectrum_rows(s_ndim, n_idx), dd = size_t(d)*d, nn = size_t(N)*N;
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N;
     const size_t row = 16*size_t(A)*N*W, out_bytes = L.outputs_end - L.outputs;
     // a spectrum of one or two dimensions with an imaginary part: Gamma is not symmetric, every weight is complex
     int complex_weights = 0;
     if (s_ndim != 3)
         for (size_t i = 0; i < s_rows*W && !complex_weights; ++i) complex_weights = spectrum[2*i + 1] != 0.0;
-    Block pin = {nullptr, 0, -1};
-    if (int rc = g_pin_pool.take(L.outputs_end, dev, &pin)) return rc;
-    unsigned char* hp = static_cast<unsigned char*>(pin.ptr);
-    auto run = [&]() -> int {
-        hipStream_t s;
-        if (int rc = resident_stream(&s)) return rc;
-        std::lock_guard<std::mutex> lock(g_arena.mu);
-        void* base = nullptr;
-        if (int rc = arena_reserve(L.end, &base)) return rc;
-        unsigned char* dp = static_cast<unsigned char*>(base);
-        // where each pulse's control matrix lies on the device: in its handle, or in the uploaded host table
-        int host_row = 0;
-        for (int p = 0; p < P; ++p) {
-            const ffk_resident* g = pulses[p];
-            const unsigned char* at;
-            if (!g)
-                at = dp + L.host + row*size_t(host_row++);
-            else if (slots[p] < 0)
-                at = static_cast<const unsigned char*>(g->dev.ptr) + g->L.R;
-            else
-                at = static_cast<const unsigned char*>(g->dev.ptr) + g->batch_R + row*size_t(slots[p]);
-            std::memcpy(hp + L.tab + 8*size_t(p), &at, 8);
-        }
-        std::memcpy(hp + L.omega, omega, 8*size_t(W));
-        std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
-        std::memcpy(hp + L.S, spectrum, 16*s_rows*W);
-        std::memcpy(hp + L.idx, idx, 4*size_t(n_idx));
-        if (n_host) std::memcpy(hp + L.host, control_matrices, row*size_t(n_host));
-        StreamDrain drain{s};
-        FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
-        const cplx* dS = reinterpret_cast<const cplx*>(dp + L.S);
-        const double* dOmega = reinterpret_cast<const double*>(dp + L.omega);
-        const int32_t* dIdx = reinterpret_cast<const int32_t*>(dp + L.idx);
-        cplx* dScale = reinterpret_cast<cplx*>(dp + L.scale);
-        double* dGamma = reinterpret_cast<double*>(dp + L.gamma);
-        double* dK = reinterpret_cast<double*>(dp + L.K);
-        int32_t* dFlags = reinterpret_cast<int32_t*>(dp + L.flags);
-        FFK_HIP(hipMemsetAsync(dFlags, 0, 4*size_t(P), s));
-        FFK_HIP(ffk::launch_spectral_weights(dS, int(s_rows), W, dOmega, W, 0, dScale, s));
-        FFK_HIP(ffk::launch_processes_decay(reinterpret_cast<const cplx* const*>(dp + L.tab), P, N, W, dScale, s_ndim,
-                                            complex_weights, dIdx, n_idx, dGamma,
-                                            reinterpret_cast<double*>(dp + L.partials), s));
-        if (stage >= 2)
-            FFK_HIP(ffk::launch_cumulant_function(dGamma, size_t(P)*pairs, N, d,
-                                                  reinterpret_cast<const cplx*>(dp + L.basis), single_qubit, dK,
-                                                  dp + L.cumulant, s));
-        if (stage >= 3)
-            FFK_HIP(ffk::launch_processes_expm(dK, P, int(pairs), N, reinterpret_cast<double*>(dp + L.U), dFlags, s));
-        FFK_HIP(hipMemcpyAsync(hp + L.outputs, dp + L.outputs, out_bytes, hipMemcpyDeviceToHost, s));
-        FFK_HIP(hipStreamSynchronize(s));
-        return kernel_fault_status();
-    };
-    const int rc = run();
-    if (!rc) {
-        if (want_gamma) std::memcpy(decay_amplitudes, hp + L.gamma, 8*size_t(P)*pairs*nn);
-        if (want_K) std::memcpy(cumulant_function, hp + L.K, 8*size_t(P)*pairs*nn);
-        if (want_U) std::memcpy(error_transfer_matrix, hp + L.U, 8*size_t(P)*nn);
-        if (not_finite) std::memcpy(not_finite, hp + L.flags, 4*size_t(P));
-    }
-    g_pin_pool.give(pin);
-    return rc;
+    PinLease pin;
+    if (int rc = pin.take(L.outputs_end, dev)) return rc;
+    unsigned char* hp = pin.ptr();
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    void* base = nullptr;
+    if (int rc = arena_reserve(L.end, &base)) return rc;
+    unsigned char* dp = static_cast<unsigned char*>(base);
+    place_host_rows(&tab, dp + L.host, row);
+    std::memcpy(hp + L.tab, tab.data(), 8*size_t(P));
+    std::memcpy(hp + L.omega, omega, 8*size_t(W));
+    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
+    stage_spectrum(spectrum, false, s_rows*W, idx, n_idx, hp + L.S, hp + L.idx);
+    if (n_host) std::memcpy(hp + L.host, control_matrices, row*size_t(n_host));
+    StreamDrain drain{s};
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    const cplx* dS = reinterpret_cast<const cplx*>(dp + L.S);
+    const double* dOmega = reinterpret_cast<const double*>(dp + L.omega);
+    const int32_t* dIdx = reinterpret_cast<const int32_t*>(dp + L.idx);
+    cplx* dScale = reinterpret_cast<cplx*>(dp + L.scale);
+    double* dGamma = reinterpret_cast<double*>(dp + L.gamma);
+    double* dK = reinterpret_cast<double*>(dp + L.K);
+    int32_t* dFlags = reinterpret_cast<int32_t*>(dp + L.flags);
+    FFK_HIP(hipMemsetAsync(dFlags, 0, 4*size_t(P), s));
+    FFK_HIP(ffk::launch_spectral_weights(dS, int(s_rows), W, dOmega, W, 0, dScale, s));
+    FFK_HIP(ffk::launch_processes_decay(reinterpret_cast<const cplx* const*>(dp + L.tab), P, N, W, dScale, s_ndim,
+                                        complex_weights, dIdx, n_idx, dGamma,
+                                        reinterpret_cast<double*>(dp + L.partials), s));
+    if (stage >= 2)
+        FFK_HIP(ffk::launch_cumulant_function(dGamma, size_t(P)*pairs, N, d,
+                                              reinterpret_cast<const cplx*>(dp + L.basis), single_qubit, dK,
+                                              dp + L.cumulant, s));
+    if (stage >= 3)
+        FFK_HIP(ffk::launch_processes_expm(dK, P, int(pairs), N, reinterpret_cast<double*>(dp + L.U), dFlags, s));
+    FFK_HIP(hipMemcpyAsync(hp + L.outputs, dp + L.outputs, out_bytes, hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    if (int rc = kernel_fault_status()) return rc;
+    if (want_gamma) std::memcpy(decay_amplitudes, hp + L.gamma, 8*size_t(P)*pairs*nn);
+    if (want_K) std::memcpy(cumulant_function, hp + L.K, 8*size_t(P)*pairs*nn);
+    if (want_U) std::memcpy(error_transfer_matrix, hp + L.U, 8*size_t(P)*nn);
+    if (not_finite) std::memcpy(not_finite, hp + L.flags, 4*size_t(P));
+    return FFK_OK;
 }
 
 }  // extern "C"
@@ -1286,7 +1247,6 @@ int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slo
 // workspace layout sliced with the size its *_workspace_bytes query reports and each slice written
 // end to end (an overrun of a slice or of the reservation is a heap-buffer-overflow under ASan).
 // ---------------------------------------------------------------------------------------------
-#include <cstring>
 #include <random>
 extern "C" int ffk_selftest_host(int rounds, unsigned seed, char* report, int report_len) {
     if (rounds < 0) {
@@ -1394,10 +1354,9 @@ extern "C" int ffk_selftest_host(int rounds, unsigned seed, char* report, int re
         }
         // (d) sequence scratch of the concatenation entry points
         {
-            const int T = pick(1, 30), Gs = pick(1, 1200), which = pick(0, 1);
+            const int Gs = pick(1, 1200), which = pick(0, 1);
             const bool herm = pick(0, 1) != 0, wantF = which == 0 && pick(0, 1);
             const int d2 = pick(2, 4), N2 = d2*d2, A2 = pick(1, 3), W2 = pick(1, 300);
-            (void)T;
             const size_t sb = sequence_scratch_bytes(Gs, d2, A2, N2, W2, which, herm, wantF);
             void* ws = std::malloc(sb);
             Bump a(ws, sb);
@@ -1440,11 +1399,30 @@ extern "C" int ffk_selftest_host(int rounds, unsigned seed, char* report, int re
             }
             for (const Block& b : held) (b.device == 0 ? g_dev_pool : g_pin_pool).give(b);
         }
-        // (f) resident layout: offsets ascending, inside the block
+        // (f) the layouts of the resident, batched, sequence and process passes: offsets ascending (no array starts
+        // inside another), every array inside `end`; where a workspace query exists, `end` is what it reports
         {
+            // (a layout is a struct of offsets declared in the order in which they are laid out)
+            auto ascending = [](const auto& L) {
+                const size_t* o = reinterpret_cast<const size_t*>(&L);
+                return std::is_sorted(o, o + sizeof(L)/sizeof(size_t));           // (`end` is the last of them)
+            };
+            const int P = pick(1, 40), n_c = pick(1, 5), T = pick(1, 30), n_host = pick(0, T);
+            const int n_idx = pick(1, A), s_ndim = pick(1, 3), n_index = P + pick(0, 500);
+            const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
             const ResidentLayout RL = resident_layout(G, d, W, N, A);
-            if (!(RL.inputs_end <= RL.D && RL.outputs_end <= RL.R && RL.R < RL.end && RL.F + 16*size_t(A)*A*W <= RL.end))
-                return -8;
+            if (!ascending(RL) || RL.infid + 8*size_t(A)*A > RL.end) return -8;
+            const BatchLayout BL = batch_layout(P, n_c, G, d, W, N, A, sh, n_idx);
+            if (!ascending(BL) || BL.R + 16*size_t(P)*A*N*W > BL.end) return -13;
+            const int As = pick(1, 4), si = pick(1, As);       // the sequence pass: d = 2, N = 4, A <= 4
+            const SeqLayout SL = seq_layout(T, P, size_t(n_index), n_host, 2, As, 4, W, spectrum_shape(s_ndim, si), si);
+            if (!ascending(SL) || SL.L + 8*size_t(T)*16 > SL.end ||
+                SL.end != ffk_concatenate_sequences_workspace_bytes(T, P, n_index, n_host, 2, As, 4, W, si, s_ndim))
+                return -14;
+            const int Np = N < 16 ? N : 16, hosts = pick(0, P);
+            const ProcLayout PL = proc_layout(P, hosts, A, Np, W, d, n_idx, s_ndim, false, true, true, true);
+            if (!ascending(PL) || PL.end != ffk_resident_batch_processes_workspace_bytes(P, hosts, A, Np, W, d, n_idx, s_ndim))
+                return -15;
             ffk_resident* h = nullptr;
             if (ffk_resident_create(&h) != FFK_OK) return -9;
             if (ffk_resident_destroy(h) != FFK_OK) return -10;

@@ -14,9 +14,9 @@ import functools
 
 import numpy as np
 
-from . import _lib, util
+from . import _lib, util      # noqa: F401  (_lib: tools/time_sequences.py reads it here)
 from ._lib import as_c128, as_f64, check
-from ._resident import Deferred, ResidentResult, _view
+from ._resident import Deferred, ResidentHandle, ResidentResult, _view, spectrum_arguments
 from .batch import MAX_PULSES, PASS_BYTES, _Member, split_passes
 
 __all__ = ['concatenate_sequences']
@@ -25,31 +25,10 @@ __all__ = ['concatenate_sequences']
 MAX_NOISE_OPERATORS = 4
 
 
-class SequencePass:
+class SequencePass(ResidentHandle):
     """Owns the ``ffk_resident`` handle of one sequence pass: the control matrices and filter functions of its
     sequences in HBM, the filter functions also in pinned host memory.  Shared by the resulting pulses, freed when
     the last of them lets go."""
-
-    def __init__(self):
-        self._lib = _lib.load()
-        self._handle = ctypes.c_void_p()
-        check(self._lib.ffk_resident_create(ctypes.byref(self._handle)))
-        self.shape = None
-
-    def __del__(self):
-        handle, self._handle = getattr(self, '_handle', None), None
-        if handle:
-            self._lib.ffk_resident_destroy(handle)
-
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (type(None), ())
-
-    @property
-    def handle(self):
-        return self._handle
 
     def evaluate(self, gates, slots, gate_table, propagators, tau, offsets, index, omega, basis, A):
         """One pass; returns (total propagators (P, 2, 2), F (P, A, A, W) viewing the handle's pinned memory)."""
@@ -85,18 +64,15 @@ class SequencePass:
         *spectrum* already validated (``util.parse_spectrum``)."""
         P, W, N, A = self.shape
         members = np.ascontiguousarray(members, dtype=np.int32)
-        idx = np.ascontiguousarray(idx, dtype=np.int32)
-        real = not np.iscomplexobj(spectrum)
-        S = as_f64(spectrum) if real else as_c128(spectrum)
-        n_idx = len(idx)
-        out = np.empty((len(members),) + ((n_idx, n_idx) if S.ndim == 3 else (n_idx,)), dtype=np.float64)
+        S, real, idx, out_shape = spectrum_arguments(spectrum, idx)
+        out = np.empty((len(members),) + out_shape, dtype=np.float64)
         if W < 2:
             out[...] = 0.0
             return out
         for a in range(0, len(members), 65535):
             part = np.ascontiguousarray(members[a:a + 65535])
             check(self._lib.ffk_resident_batch_infidelity(self._handle, part.ctypes.data, len(part), S.ctypes.data,
-                                                          S.ndim, int(real), idx.ctypes.data, n_idx, int(d),
+                                                          S.ndim, real, idx.ctypes.data, len(idx), int(d),
                                                           out[a:a + 65535].ctypes.data))
         return out
 

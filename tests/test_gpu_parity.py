@@ -2786,6 +2786,107 @@ def test_resident_pass_from_controls(d, G, n_c):
         b.evaluate(c_opers, dt, t, omega, basis, n_opers, n_coeffs, c_coeffs=c_coeffs[:, :-1])
 
 
+def test_one_handle_through_every_kind_of_pass():
+    """One ffk_resident handle filled in turn by a single pass, a batched pass, a sequence pass and a single pass
+    again: after each, the readers of that kind serve it and the readers of the other kind refuse it; a call
+    rejected for its arguments leaves the handle as it was; gates and pulses read in place from single results and
+    from members give what host arrays give.  (The three Python owners share one base class: the methods of one
+    are called on the handle of another.)"""
+    import ctypes
+    from filter_functions_amd._resident import ResidentResult
+    from filter_functions_amd.batch import BatchResult
+    from filter_functions_amd.sequences import SequencePass
+    lib = _lib.load()
+    d, G, W, A, N, P, n_c = 2, 3, 8, 2, 4, 3, 2
+    rng = np.random.default_rng(11)
+
+    def rand_herm(*lead):
+        M = rng.standard_normal(lead + (d, d)) + 1j*rng.standard_normal(lead + (d, d))
+        return (M + M.conj().swapaxes(-1, -2))/2
+    c_opers, c_coeffs = rand_herm(P, n_c), rng.standard_normal((P, n_c, G))
+    n_opers, n_coeffs = rand_herm(P, A), rng.random((P, A, G)) + 0.5
+    dt = rng.random((P, G)) + 0.1
+    t = np.concatenate([np.zeros((P, 1)), dt.cumsum(axis=1)], axis=1)
+    omega = np.geomspace(0.1, 10, W)
+    basis = np.asarray(ff.Basis.pauli(1))
+    S, idx = 1e-3/omega, np.array([0, 1], dtype=np.int32)
+    out = np.empty(2)
+
+    def single(res, p=0):
+        return res.evaluate(c_opers[p], dt[p], t[p], omega, basis, n_opers[p], n_coeffs[p], c_coeffs=c_coeffs[p])
+
+    def batched(res, n=P):
+        return BatchResult.evaluate(res, c_opers[:n], c_coeffs[:n], dt[:n], t[:n], omega, basis, n_opers[:n],
+                                    n_coeffs[:n])
+
+    def integral(res, idx):
+        idx = np.asarray(idx, dtype=np.int32)
+        return lib.ffk_resident_infidelity(res.handle, S.ctypes.data, 1, 1, idx.ctypes.data, len(idx), d,
+                                           out.ctypes.data)
+
+    def single_readers(res):
+        R, at = np.empty((A, N, W), dtype=complex), ctypes.c_void_p()
+        return (lib.ffk_resident_control_matrix(res.handle, R.ctypes.data),
+                lib.ffk_resident_control_matrix_dev(res.handle, ctypes.byref(at), None, None), integral(res, [0, 1]))
+
+    def member(res, k):
+        R = np.empty((A, N, W), dtype=complex)
+        return lib.ffk_resident_batch_control_matrix(res.handle, k, R.ctypes.data), R
+
+    # 1. a single pass
+    h = ResidentResult()
+    D1, _, Q1, F1 = (x.copy() for x in single(h))
+    R1, infid1 = h.control_matrix(), h.infidelity(S, idx, d)
+    # 2., 3. calls rejected for their arguments leave it as it was
+    assert integral(h, [0, 2]) == _lib.FFK_EINVAL and 'idx' in lib.ffk_last_error().decode()
+    assert np.array_equal(h.control_matrix(), R1)
+    with pytest.raises(ValueError):
+        batched(h, 0)
+    assert np.array_equal(h.control_matrix(), R1) and single_readers(h) == (0, 0, 0)
+    # 4. a batched pass: the single readers refuse, the members are those of a fresh handle
+    batched(h)
+    assert single_readers(h) == (_lib.FFK_EINVAL,)*3
+    fresh = BatchResult()
+    Qb = batched(fresh)[2]
+    for k in range(P):
+        rc, R = member(h, k)
+        assert rc == 0 and rel_err(R, fresh.control_matrix(k)) < 1e-12
+    assert member(h, P)[0] == _lib.FFK_EINVAL and member(h, -1)[0] == _lib.FFK_EINVAL
+    # 5. a sequence pass whose gates are a single result and a member of a batch
+    a = ResidentResult()
+    Qa = single(a)[2]
+    U, tau = np.array([Qa[-1], Qb[1][-1]]), np.array([dt[0].sum(), dt[1].sum()])
+    offsets, index = [0, 2, 5], [0, 1, 1, 0, 1]
+    gates = [a.handle.value, fresh.handle.value], [-1, 1], None
+    table = np.array([a.control_matrix(), fresh.control_matrix(1)])
+    total_h, F_h = SequencePass.evaluate(h, *gates, U, tau, offsets, index, omega, basis, A)
+    F_h, R_h = F_h.copy(), [SequencePass.control_matrix(h, j) for j in range(2)]
+    assert single_readers(h) == (_lib.FFK_EINVAL,)*3
+    for other, args in ((SequencePass(), gates), (SequencePass(), ([None, None], [-1, -1], table))):
+        total, F = other.evaluate(*args, U, tau, offsets, index, omega, basis, A)
+        assert rel_err(total, total_h) < 1e-13 and rel_err(F, F_h) < 1e-12
+        assert all(rel_err(other.control_matrix(j), R_h[j]) < 1e-12 for j in range(2))
+    # 6. decay amplitudes of the two members, a single result and a host array, against four host arrays
+    Sc = S.astype(complex)
+
+    def decay(handles, slots, table):
+        gamma = np.empty((4, 2, N, N))
+        slots, table = np.array(slots, dtype=np.int32), np.ascontiguousarray(table)
+        _lib.check(lib.ffk_resident_batch_processes(
+            (ctypes.c_void_p*4)(*handles), slots.ctypes.data, table.ctypes.data, 4, A, N, W, d, omega.ctypes.data,
+            basis.ctypes.data, 1, Sc.ctypes.data, 1, idx.ctypes.data, 2, gamma.ctypes.data, None, None, None))
+        return gamma
+    last = fresh.control_matrix(2)
+    gamma = decay([h.handle.value, h.handle.value, a.handle.value, None], [0, 1, -1, -1], last[None])
+    assert rel_err(gamma, decay([None]*4, [-1]*4, np.array(R_h + [table[0], last]))) < 1e-12
+    # 7. the single pass again: the same results, the single readers serve it, the batched reader refuses
+    D, V, Q, F = single(h)
+    assert rel_err(D, D1) < 1e-13 and rel_err(Q, Q1) < 1e-13 and rel_err(F, F1) < 1e-12
+    assert rel_err(h.control_matrix(), R1) < 1e-12 and single_readers(h) == (0, 0, 0)
+    assert rel_err(h.infidelity(S, idx, d), infid1) < 1e-12
+    assert member(h, 0)[0] == _lib.FFK_EINVAL
+
+
 def test_copies_and_pickles_of_a_pulse_with_a_resident_result():
     """deepcopy / pickle of a pulse whose control matrix still lives in HBM: the copy holds host
     arrays and no device memory, the original keeps working, both give the same numbers."""

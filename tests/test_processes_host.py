@@ -79,6 +79,15 @@ def test_bytes_counted_per_pass_cover_the_workspace_query(A, N, W, d, n_idx, s_n
             assert counted - need <= fixed + 16*256, (P, host)
 
 
+@pytest.mark.parametrize('args,nbytes', [((1, 0, 1, 4, 1, 2, 1, 1), 5376), ((3, 1, 2, 4, 8, 2, 2, 3), 20992),
+                                         ((64, 0, 3, 16, 4096, 4, 3, 1), 10534656),
+                                         ((5, 5, 4, 9, 300, 3, 4, 2), 1090560),
+                                         ((7, 0, 1, 16, 257, 4, 1, 3), 213248)])
+def test_workspace_query_values(args, nbytes):
+    """The layout of the pass is part of what callers size their passes by: recorded values."""
+    assert _lib.load().ffk_resident_batch_processes_workspace_bytes(*args) == nbytes
+
+
 def test_workspace_query_rejects_what_the_entry_rejects():
     q = _lib.load().ffk_resident_batch_processes_workspace_bytes
     assert q(64, 0, 3, 16, 4096, 4, 3, 1) > 0

@@ -101,6 +101,16 @@ def test_workspace_query_needs_no_gpu():
     assert lib.ffk_concatenate_sequences_workspace_bytes(24, 2, 20, 0, 2, 1, 4, 301, 1, 1) > more
 
 
+@pytest.mark.parametrize('args,nbytes', [((24, 1, 10, 0, 2, 1, 4, 301, 0, 0), 148992),
+                                         ((24, 2, 20, 0, 2, 1, 4, 301, 0, 0), 173056),
+                                         ((24, 2, 20, 3, 2, 2, 4, 301, 2, 2), 366336),
+                                         ((3, 2, 5, 1, 2, 4, 4, 7, 4, 3), 14592),
+                                         ((1, 1, 1, 0, 2, 1, 4, 1, 1, 1), 4096)])
+def test_workspace_query_values(args, nbytes):
+    """The layout of the pass is part of what callers size their passes by: recorded values."""
+    assert _lib.load().ffk_concatenate_sequences_workspace_bytes(*args) == nbytes
+
+
 def test_new_kernels_resources(kernels):  # noqa: F811
     found = {name: k for name, k in kernels.items() if 'sequences_' in name and 'kernel' in name}
     assert sum('sequences_front_kernel' in n for n in found) == 1

@@ -309,16 +309,7 @@ int ffk_event_elapsed_ms(void* start, void* stop, float* ms) {
     FFK_HIP(hipEventElapsedTime(ms, static_cast<hipEvent_t>(start), static_cast<hipEvent_t>(stop)));
     return FFK_OK;
 }
-int ffk_release_arena(void) {
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    if (g_arena.ptr) {
-        FFK_HIP(hipDeviceSynchronize());
-        FFK_HIP(hipFree(g_arena.ptr));
-        g_arena.ptr = nullptr;
-        g_arena.size = 0;
-    }
-    return FFK_OK;
-}
+int ffk_release_arena(void) { return arena_release(); }
 
 int ffk_set_segment_chunks(int chunks) {
     FFK_REQUIRE(chunks >= 0, "chunks must be >= 0");
@@ -404,30 +395,22 @@ int ffk_diagonalize(const double* hamiltonian, const double* dt, int G, int d, d
     FFK_REQUIRE(d_ok(d), "unsupported dimension d=%d (need 2 <= d <= %d)", d, FFK_MAX_D);
     FFK_REQUIRE(G >= 1, "need at least one segment, got G=%d", G);
     FFK_REQUIRE(hamiltonian && dt && eigvals && eigvecs && propagators, "NULL argument");
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nH = sizeof(cplx)*size_t(G)*d*d, nQ = sizeof(cplx)*size_t(G + 1)*d*d;
+    StagedCall c;
     const size_t wsb = ffk_diagonalize_workspace_bytes(G, d);
-    const size_t total = 2*align_up(nH) + align_up(nQ) + 2*align_up(sizeof(double)*G*d) + wsb;
-    void* base;
-    if (int rc = arena_reserve(total, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dH = a.take<double>(size_t(G)*d*d*2);
-    double* ddt = a.take<double>(G);
-    double* dD = a.take<double>(size_t(G)*d);
-    double* dV = a.take<double>(size_t(G)*d*d*2);
-    double* dQ = a.take<double>(size_t(G + 1)*d*d*2);
-    void* ws = a.take<unsigned char>(wsb);
-    FFK_REQUIRE(ws, "internal: arena too small");
-    FFK_HIP(hipMemcpyAsync(dH, hamiltonian, nH, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(ddt, dt, sizeof(double)*G, hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_diagonalize_dev(dH, ddt, G, d, dD, dV, dQ, ws, wsb, nullptr)) return rc;
+    const auto H = c.in<double>(hamiltonian, 2*size_t(G)*d*d);
+    const auto sdt = c.in<double>(dt, G);
+    const auto D = c.out<double>(size_t(G)*d);
+    const auto V = c.out<double>(2*size_t(G)*d*d);
+    const auto Q = c.out<double>(2*size_t(G + 1)*d*d);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_diagonalize_dev(c[H], c[sdt], G, d, c[D], c[V], c[Q], c[ws], wsb, nullptr)) return rc;
     std::vector<int> flags(G, 0);
-    const int* dstatus = slice_diag_ws(ws, wsb, G, d).status;
-    FFK_HIP(hipMemcpyAsync(eigvals, dD, sizeof(double)*G*d, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipMemcpyAsync(eigvecs, dV, nH, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipMemcpyAsync(propagators, dQ, nQ, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipMemcpyAsync(flags.data(), dstatus, sizeof(int)*G, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
+    if (int rc = c.copy_back(eigvals, D)) return rc;
+    if (int rc = c.copy_back(eigvecs, V)) return rc;
+    if (int rc = c.copy_back(propagators, Q)) return rc;
+    if (int rc = c.d2h(flags.data(), slice_diag_ws(c[ws], wsb, G, d).status, sizeof(int)*size_t(G))) return rc;
+    if (int rc = c.finish()) return rc;
     int status = 0;
     for (int f : flags) status += f;
     if (status != 0)
@@ -569,54 +552,27 @@ int ffk_control_matrix(const double* eigvals, const double* eigvecs, const doubl
     FFK_REQUIRE(eigvals && eigvecs && propagators && omega && n_opers && n_coeffs && dt && t,
                 "NULL argument");
     if (int rc = kernel_fault_stale()) return rc;
-    std::lock_guard<std::mutex> lock(g_arena.mu);
+    StagedCall c;
     const size_t dd = size_t(d)*d;
     const size_t wsb = ffk_control_matrix_workspace_bytes(W, N, A, G, d);
     const bool want_R = control_matrix != nullptr;
     const bool want_B = (flags & FFK_WANT_NOISE_OPERATORS) != 0;
-    size_t total = wsb;
-    total += align_up(8*size_t(G)*d) + align_up(16*size_t(G)*dd) + align_up(16*size_t(G + 1)*dd);
-    total += align_up(8*size_t(W)) + align_up(16*size_t(N)*dd) + align_up(16*size_t(A)*dd);
-    total += align_up(8*size_t(A)*G) + align_up(8*size_t(G)) + align_up(8*size_t(G + 1));
-    if (want_R) total += align_up(16*size_t(A)*N*W);
-    if (want_B) total += align_up(16*size_t(A)*dd*W);
-    void* base;
-    if (int rc = arena_reserve(total, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dD = a.take<double>(size_t(G)*d);
-    double* dV = a.take<double>(2*size_t(G)*dd);
-    double* dQ = a.take<double>(2*size_t(G + 1)*dd);
-    double* dom = a.take<double>(W);
-    double* dbasis = a.take<double>(2*size_t(N)*dd);
-    double* dnop = a.take<double>(2*size_t(A)*dd);
-    double* dnc = a.take<double>(size_t(A)*G);
-    double* ddt = a.take<double>(G);
-    double* dtt = a.take<double>(G + 1);
-    double* dR = want_R ? a.take<double>(2*size_t(A)*N*W) : nullptr;
-    double* dB = want_B ? a.take<double>(2*size_t(A)*dd*W) : nullptr;
-    void* ws = a.take<unsigned char>(wsb);
-    FFK_REQUIRE(ws, "internal: arena too small");
-    auto h2d = [](void* dst, const void* src, size_t n) {
-        return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, nullptr);
-    };
-    FFK_HIP(h2d(dD, eigvals, 8*size_t(G)*d));
-    FFK_HIP(h2d(dV, eigvecs, 16*size_t(G)*dd));
-    FFK_HIP(h2d(dQ, propagators, 16*size_t(G + 1)*dd));
-    FFK_HIP(h2d(dom, omega, 8*size_t(W)));
-    if (basis) FFK_HIP(h2d(dbasis, basis, 16*size_t(N)*dd));
-    FFK_HIP(h2d(dnop, n_opers, 16*size_t(A)*dd));
-    FFK_HIP(h2d(dnc, n_coeffs, 8*size_t(A)*G));
-    FFK_HIP(h2d(ddt, dt, 8*size_t(G)));
-    FFK_HIP(h2d(dtt, t, 8*size_t(G + 1)));
-    if (int rc = ffk_control_matrix_dev(dD, dV, dQ, dom, W, basis ? dbasis : nullptr, N, dnop, A, dnc,
-                                        ddt, dtt, G, d, flags, dR, dB, ws, wsb, nullptr))
+    const PulseSlices p = stage_pulse(c, eigvals, eigvecs, propagators, omega, W, basis, N, n_opers, A, n_coeffs, dt,
+                                      t, G, d);
+    const auto R = c.out<double>(want_R ? 2*size_t(A)*N*W : 0);
+    const auto B = c.out<double>(want_B ? 2*size_t(A)*dd*W : 0);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_control_matrix_dev(c[p.eigvals], c[p.eigvecs], c[p.propagators], c[p.omega], W,
+                                        basis ? c[p.basis] : nullptr, N, c[p.n_opers], A, c[p.n_coeffs], c[p.dt],
+                                        c[p.t], G, d, flags, want_R ? c[R] : nullptr, want_B ? c[B] : nullptr, c[ws],
+                                        wsb, nullptr))
         return rc;
     if (want_R)
-        FFK_HIP(hipMemcpyAsync(control_matrix, dR, 16*size_t(A)*N*W, hipMemcpyDeviceToHost, nullptr));
+        if (int rc = c.copy_back(control_matrix, R)) return rc;
     if (want_B)
-        FFK_HIP(hipMemcpyAsync(noise_operators, dB, 16*size_t(A)*dd*W, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return kernel_fault_status();
+        if (int rc = c.copy_back(noise_operators, B)) return rc;
+    return c.finish_with_fault_status();
 }
 
 static int intermediates_impl(const double* eigvals, const double* eigvecs,
@@ -634,64 +590,45 @@ static int intermediates_impl(const double* eigvals, const double* eigvecs,
     FFK_REQUIRE(basis || !(basis_transformed || control_matrix_step), "basis is NULL");
     FFK_REQUIRE(size_t(G)*A <= 65535, "G*A = %zu too large for the materialising variant", size_t(G)*A);
     if (int rc = kernel_fault_stale()) return rc;
-    std::lock_guard<std::mutex> lock(g_arena.mu);
+    StagedCall c;
     const size_t dd = size_t(d)*d;
+    const bool want_steps = control_matrix_step || noise_operators_step;
     // inputs + operands + every requested product, all resident at once (HBM is 288 GB)
-    size_t total = 0;
-    total += align_up(8*size_t(G)*d) + align_up(16*size_t(G)*dd) + align_up(16*size_t(G + 1)*dd);
-    total += align_up(8*size_t(W)) + align_up(16*size_t(N)*dd) + align_up(16*size_t(A)*dd);
-    total += align_up(8*size_t(A)*G) + align_up(8*size_t(G)) + align_up(8*size_t(G + 1));
-    total += align_up(8*size_t(G)*ffk::seg_stride(d)) + align_up(16*size_t(G)*dd) +
-             align_up(16*size_t(G)*(1 + A)*dd);
-    total += align_up(16*size_t(A)*G*dd) + align_up(16*size_t(G)*dd);          // nt, ep
-    if (basis_transformed) total += align_up(16*size_t(G)*N*dd);
-    if (phase_factors) total += align_up(16*size_t(G)*W);
-    if (first_order_integral) total += align_up(16*size_t(G)*W*dd);
-    if (control_matrix_step || noise_operators_step) total += align_up(16*size_t(G)*A*dd*W);
-    if (control_matrix_step)
-        total += align_up(16*size_t(G)*A*N*W) + ffk::expand_workspace_bytes(N, d);
-    if (noise_operators_step) total += align_up(16*size_t(G)*W*A*dd);
-    void* base;
-    if (int rc = arena_reserve(total, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dD = a.take<double>(size_t(G)*d);
-    cplx* dV = a.take<cplx>(size_t(G)*dd);
-    cplx* dQ = a.take<cplx>(size_t(G + 1)*dd);
-    double* dom = a.take<double>(W);
-    cplx* dbasis = a.take<cplx>(size_t(N)*dd);
-    cplx* dnop = a.take<cplx>(size_t(A)*dd);
-    double* dnc = a.take<double>(size_t(A)*G);
-    double* ddt = a.take<double>(G);
-    double* dtt = a.take<double>(G + 1);
-    double* segtab = a.take<double>(size_t(G)*ffk::seg_stride(d));
-    cplx* Tc = a.take<cplx>(size_t(G)*dd);
-    cplx* ops = a.take<cplx>(size_t(G)*(1 + A)*dd);
-    cplx* dnt = a.take<cplx>(size_t(A)*G*dd);
-    cplx* dep = a.take<cplx>(size_t(G)*dd);
-    cplx* dbt = basis_transformed ? a.take<cplx>(size_t(G)*N*dd) : nullptr;
-    cplx* dph = phase_factors ? a.take<cplx>(size_t(G)*W) : nullptr;
-    cplx* dint = first_order_integral ? a.take<cplx>(size_t(G)*W*dd) : nullptr;
-    cplx* Ypart = (control_matrix_step || noise_operators_step) ? a.take<cplx>(size_t(G)*A*dd*W) : nullptr;
-    cplx* dnstep = noise_operators_step ? a.take<cplx>(size_t(G)*W*A*dd) : nullptr;
-    cplx* dstep = control_matrix_step ? a.take<cplx>(size_t(G)*A*N*W) : nullptr;
-    void* dews = control_matrix_step ? a.take<unsigned char>(ffk::expand_workspace_bytes(N, d)) : nullptr;
-    FFK_REQUIRE(a.used <= g_arena.size, "internal: arena too small");
-    auto h2d = [](void* dst, const void* src, size_t n) {
-        return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, nullptr);
-    };
-    auto d2h = [](void* dst, const void* src, size_t n) {
-        return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, nullptr);
-    };
-    FFK_HIP(h2d(dD, eigvals, 8*size_t(G)*d));
-    FFK_HIP(h2d(dV, eigvecs, 16*size_t(G)*dd));
-    FFK_HIP(h2d(dQ, propagators, 16*size_t(G + 1)*dd));
-    FFK_HIP(h2d(dom, omega, 8*size_t(W)));
-    if (basis) FFK_HIP(h2d(dbasis, basis, 16*size_t(N)*dd));
-    FFK_HIP(h2d(dnop, n_opers, 16*size_t(A)*dd));
-    FFK_HIP(h2d(dnc, n_coeffs, 8*size_t(A)*G));
-    FFK_HIP(h2d(ddt, dt, 8*size_t(G)));
-    FFK_HIP(h2d(dtt, t, 8*size_t(G + 1)));
-    FFK_HIP(ffk::launch_prologue(dD, dV, dQ, dnop, dnc, ddt, dtt, G, d, A, segtab, Tc, ops, dnt, dep, nullptr));
+    const PulseSlices p = stage_pulse(c, eigvals, eigvecs, propagators, omega, W, basis, N, n_opers, A, n_coeffs, dt,
+                                      t, G, d);
+    const auto s_segtab = c.out<double>(size_t(G)*ffk::seg_stride(d));
+    const auto s_Tc = c.out<cplx>(size_t(G)*dd);
+    const auto s_ops = c.out<cplx>(size_t(G)*(1 + A)*dd);
+    const auto s_nt = c.out<cplx>(size_t(A)*G*dd);
+    const auto s_ep = c.out<cplx>(size_t(G)*dd);
+    const auto s_bt = c.out<cplx>(basis_transformed ? size_t(G)*N*dd : 0);
+    const auto s_ph = c.out<cplx>(phase_factors ? size_t(G)*W : 0);
+    const auto s_int = c.out<cplx>(first_order_integral ? size_t(G)*W*dd : 0);
+    const auto s_Y = c.out<cplx>(want_steps ? size_t(G)*A*dd*W : 0);
+    const auto s_nstep = c.out<cplx>(noise_operators_step ? size_t(G)*W*A*dd : 0);
+    const auto s_step = c.out<cplx>(control_matrix_step ? size_t(G)*A*N*W : 0);
+    const auto s_ews = c.out<unsigned char>(control_matrix_step ? ffk::expand_workspace_bytes(N, d) : 0);
+    if (int rc = c.stage()) return rc;
+    const double* dD = c[p.eigvals];
+    const double* dom = c[p.omega];
+    const double* ddt = c[p.dt];
+    const double* dtt = c[p.t];
+    const cplx* dbasis = reinterpret_cast<const cplx*>(c[p.basis]);
+    double* segtab = c[s_segtab];
+    cplx* Tc = c[s_Tc];
+    cplx* ops = c[s_ops];
+    cplx* dnt = c[s_nt];
+    cplx* dep = c[s_ep];
+    cplx* dbt = basis_transformed ? c[s_bt] : nullptr;
+    cplx* dph = phase_factors ? c[s_ph] : nullptr;
+    cplx* dint = first_order_integral ? c[s_int] : nullptr;
+    cplx* Ypart = want_steps ? c[s_Y] : nullptr;
+    cplx* dnstep = noise_operators_step ? c[s_nstep] : nullptr;
+    cplx* dstep = control_matrix_step ? c[s_step] : nullptr;
+    FFK_HIP(ffk::launch_prologue(dD, reinterpret_cast<const cplx*>(c[p.eigvecs]),
+                                 reinterpret_cast<const cplx*>(c[p.propagators]),
+                                 reinterpret_cast<const cplx*>(c[p.n_opers]), c[p.n_coeffs], ddt, dtt, G, d, A, segtab,
+                                 Tc, ops, dnt, dep, nullptr));
     if (dbt) FFK_HIP(ffk::launch_basis_transformed(Tc, dbasis, G, N, d, dbt, nullptr));
     FFK_HIP(ffk::launch_phase_and_integral(dom, W, segtab, G, d, dph, dint, nullptr));
     if (Ypart) {
@@ -700,20 +637,26 @@ static int intermediates_impl(const double* eigvals, const double* eigvecs,
         FFK_HIP(ffk::launch_accumulate(dom, W, segtab, ops, G, d, A, geo, Ypart, nullptr));
     }
     if (dstep)    // ... expanded in the basis
-        FFK_HIP(ffk::launch_expand(Ypart, dbasis, G*A, N, d, W, dstep, dews, false, nullptr));
+        FFK_HIP(ffk::launch_expand(Ypart, dbasis, G*A, N, d, W, dstep, c[s_ews], false, nullptr));
     if (dnstep)   // ... or re-laid out as (W, A, d, d) per segment
         for (int g = 0; g < G; ++g)
             FFK_HIP(ffk::launch_transpose_noise_ops(Ypart + size_t(g)*A*dd*W, A, d, W,
                                                     dnstep + size_t(g)*W*A*dd, nullptr));
-    if (n_opers_transformed) FFK_HIP(d2h(n_opers_transformed, dnt, 16*size_t(A)*G*dd));
-    if (eigvecs_propagated) FFK_HIP(d2h(eigvecs_propagated, dep, 16*size_t(G)*dd));
-    if (basis_transformed) FFK_HIP(d2h(basis_transformed, dbt, 16*size_t(G)*N*dd));
-    if (phase_factors) FFK_HIP(d2h(phase_factors, dph, 16*size_t(G)*W));
-    if (first_order_integral) FFK_HIP(d2h(first_order_integral, dint, 16*size_t(G)*W*dd));
-    if (control_matrix_step) FFK_HIP(d2h(control_matrix_step, dstep, 16*size_t(G)*A*N*W));
-    if (noise_operators_step) FFK_HIP(d2h(noise_operators_step, dnstep, 16*size_t(G)*W*A*dd));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return kernel_fault_status();
+    if (n_opers_transformed)
+        if (int rc = c.copy_back(n_opers_transformed, s_nt)) return rc;
+    if (eigvecs_propagated)
+        if (int rc = c.copy_back(eigvecs_propagated, s_ep)) return rc;
+    if (basis_transformed)
+        if (int rc = c.copy_back(basis_transformed, s_bt)) return rc;
+    if (phase_factors)
+        if (int rc = c.copy_back(phase_factors, s_ph)) return rc;
+    if (first_order_integral)
+        if (int rc = c.copy_back(first_order_integral, s_int)) return rc;
+    if (control_matrix_step)
+        if (int rc = c.copy_back(control_matrix_step, s_step)) return rc;
+    if (noise_operators_step)
+        if (int rc = c.copy_back(noise_operators_step, s_nstep)) return rc;
+    return c.finish_with_fault_status();
 }
 
 int ffk_control_matrix_intermediates(const double* eigvals, const double* eigvecs,
@@ -770,20 +713,14 @@ int ffk_filter_function_weighted(const double* control_matrix, int A, int N, int
                                  const double* weights, double scale, double* filter_function) {
     FFK_REQUIRE(control_matrix && weights && filter_function, "NULL argument");
     FFK_REQUIRE(A >= 1 && N >= 1 && W >= 1, "empty axis: A=%d N=%d W=%d", A, N, W);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nR = 16*size_t(A)*N*W, nM = 16*size_t(N)*N, nF = 16*size_t(A)*A*W;
-    void* base;
-    if (int rc = arena_reserve(align_up(nR) + align_up(nM) + align_up(nF), &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dR = a.take<double>(nR/8);
-    double* dM = a.take<double>(nM/8);
-    double* dF = a.take<double>(nF/8);
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix, nR, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dM, weights, nM, hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_filter_function_weighted_dev(dR, A, N, W, dM, scale, dF, nullptr)) return rc;
-    FFK_HIP(hipMemcpyAsync(filter_function, dF, nF, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    StagedCall c;
+    const auto R = c.in<double>(control_matrix, 2*size_t(A)*N*W);
+    const auto M = c.in<double>(weights, 2*size_t(N)*N);
+    const auto F = c.out<double>(2*size_t(A)*A*W);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_filter_function_weighted_dev(c[R], A, N, W, c[M], scale, c[F], nullptr)) return rc;
+    if (int rc = c.copy_back(filter_function, F)) return rc;
+    return c.finish();
 }
 
 int ffk_filter_function(const double* control_matrix, int A, int N, int W, int which,
@@ -791,19 +728,13 @@ int ffk_filter_function(const double* control_matrix, int A, int N, int W, int w
     FFK_REQUIRE(control_matrix && filter_function, "NULL argument");
     FFK_REQUIRE(A >= 1 && N >= 1 && W >= 1, "empty axis: A=%d N=%d W=%d", A, N, W);
     FFK_REQUIRE(which == FFK_FF_FIDELITY || which == FFK_FF_GENERALIZED, "invalid which=%d", which);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nR = 16*size_t(A)*N*W;
-    const size_t nF = which == FFK_FF_FIDELITY ? 16*size_t(A)*A*W : 16*size_t(A)*A*N*N*W;
-    void* base;
-    if (int rc = arena_reserve(align_up(nR) + align_up(nF), &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dR = a.take<double>(nR/8);
-    double* dF = a.take<double>(nF/8);
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix, nR, hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_filter_function_dev(dR, A, N, W, which, dF, nullptr)) return rc;
-    FFK_HIP(hipMemcpyAsync(filter_function, dF, nF, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    StagedCall c;
+    const auto R = c.in<double>(control_matrix, 2*size_t(A)*N*W);
+    const auto F = c.out<double>(which == FFK_FF_FIDELITY ? 2*size_t(A)*A*W : 2*size_t(A)*A*N*N*W);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_filter_function_dev(c[R], A, N, W, which, c[F], nullptr)) return rc;
+    if (int rc = c.copy_back(filter_function, F)) return rc;
+    return c.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -858,31 +789,20 @@ int ffk_infidelity(const double* filter_function, int A, int W, const double* sp
     FFK_REQUIRE(A >= 1 && W >= 1 && n_idx >= 1 && d >= 1, "empty axis");
     for (int i = 0; i < n_idx; ++i)
         FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "noise operator index %d out of range [0, %d)", idx[i], A);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nout = s_ndim == 3 ? size_t(n_idx)*n_idx : n_idx;
-    const size_t nS = 16*size_t(W)*(s_ndim == 1 ? 1 : (s_ndim == 2 ? n_idx : size_t(n_idx)*n_idx));
-    const size_t nF = 16*size_t(A)*A*W;
+    StagedCall c;
+    const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
     const size_t wsb = ffk_infidelity_workspace_bytes(W, n_idx, s_ndim);
-    void* base;
-    if (int rc = arena_reserve(align_up(nF) + align_up(nS) + align_up(8*size_t(W)) + align_up(4*size_t(n_idx)) +
-                                   align_up(8*nout) + wsb, &base))
+    const auto F = c.in<double>(filter_function, 2*size_t(A)*A*W);
+    const auto S = c.in<double>(spectrum, 2*size_t(W)*sh.rows);
+    const auto om = c.in<double>(omega, W);
+    const auto didx = c.in<int32_t>(idx, n_idx);
+    const auto out = c.out<double>(sh.n_out);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_infidelity_dev(c[F], A, W, c[S], s_ndim, c[om], c[didx], n_idx, d, c[out], c[ws], wsb, nullptr))
         return rc;
-    Bump a(base, g_arena.size);
-    double* dF = a.take<double>(nF/8);
-    double* dS = a.take<double>(nS/8);
-    double* dom = a.take<double>(W);
-    int32_t* didx = a.take<int32_t>(n_idx);
-    double* dout = a.take<double>(nout);
-    void* ws = a.take<unsigned char>(wsb);
-    FFK_HIP(hipMemcpyAsync(dF, filter_function, nF, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dS, spectrum, nS, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dom, omega, 8*size_t(W), hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(didx, idx, 4*size_t(n_idx), hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_infidelity_dev(dF, A, W, dS, s_ndim, dom, didx, n_idx, d, dout, ws, wsb, nullptr))
-        return rc;
-    FFK_HIP(hipMemcpyAsync(infid, dout, 8*nout, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    if (int rc = c.copy_back(infid, out)) return rc;
+    return c.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -911,24 +831,17 @@ int ffk_liouville(const double* U, int batch, int d, const double* basis, int N,
     FFK_REQUIRE(d_ok(d), "unsupported dimension d=%d (need 2 <= d <= %d)", d, FFK_MAX_D);
     FFK_REQUIRE(batch >= 1 && N >= 1, "empty axis: batch=%d N=%d", batch, N);
     FFK_REQUIRE(U && basis && liouville, "NULL argument");
-    std::lock_guard<std::mutex> lock(g_arena.mu);
+    StagedCall c;
     const size_t dd = size_t(d)*d;
-    const size_t nU = 16*size_t(batch)*dd, nB = 16*size_t(N)*dd;
-    const size_t nL = (hermitian_basis ? 8 : 16)*size_t(batch)*N*N;
     const size_t wsb = ffk_liouville_workspace_bytes(batch, d, N);
-    void* base;
-    if (int rc = arena_reserve(align_up(nU) + align_up(nB) + align_up(nL) + wsb, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dU = a.take<double>(nU/8);
-    double* dB = a.take<double>(nB/8);
-    double* dL = a.take<double>(nL/8);
-    void* ws = a.take<unsigned char>(wsb);
-    FFK_HIP(hipMemcpyAsync(dU, U, nU, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dB, basis, nB, hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_liouville_dev(dU, batch, d, dB, N, hermitian_basis, dL, ws, wsb, nullptr)) return rc;
-    FFK_HIP(hipMemcpyAsync(liouville, dL, nL, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    const auto dU = c.in<double>(U, 2*size_t(batch)*dd);
+    const auto B = c.in<double>(basis, 2*size_t(N)*dd);
+    const auto L = c.out<double>((hermitian_basis ? 1 : 2)*size_t(batch)*N*N);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_liouville_dev(c[dU], batch, d, c[B], N, hermitian_basis, c[L], c[ws], wsb, nullptr)) return rc;
+    if (int rc = c.copy_back(liouville, L)) return rc;
+    return c.finish();
 }
 
 // ---------------------------------------------------------------------------------------------

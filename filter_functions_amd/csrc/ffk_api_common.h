@@ -1,6 +1,7 @@
 // ffk_api_common.h -- what the translation units of the extern "C" surface (ffk_api*.hip) share:
 // error reporting, argument checks, the bump allocator over workspaces, the process-wide staging
-// arena, workspace layouts used by more than one family of entry points.
+// arena and the one scoped object through which the host-pointer entry points use it (StagedCall),
+// the shape of a spectrum, workspace layouts used by more than one family of entry points.
 //
 //   ffk_api.hip           device / stream utilities, diagonalize, control matrix, filter function,
 //                         infidelity, Liouville representation, the fused pipeline pass (SURVEY 8 a)
@@ -48,6 +49,9 @@ hipError_t stub_free(void* p) {
 #define hipGetDevice(d) ((*(d) = 0), hipSuccess)
 #define hipSetDevice(d) hipSuccess
 #define hipDeviceSynchronize() hipSuccess
+// the arena is on the C heap here, so what StagedCall copies to and from it is a plain copy (tools/check_staged_call.hip)
+#define hipMemcpyAsync(dst, src, n, kind, stream) (std::memcpy((dst), (src), (n)), hipSuccess)
+#define hipStreamSynchronize(stream) hipSuccess
 #endif
 
 using ffk::align_up;
@@ -177,6 +181,135 @@ struct Arena {
 };
 extern Arena g_arena;
 int arena_reserve(size_t bytes, void** out);
+// ffk_release_arena
+inline int arena_release() {
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    if (g_arena.ptr) {
+        FFK_HIP(hipDeviceSynchronize());
+        FFK_HIP(hipFree(g_arena.ptr));
+        g_arena.ptr = nullptr;
+        g_arena.size = 0;
+    }
+    return FFK_OK;
+}
+
+// One call of the host-pointer flavour: the only place that locks the arena, reserves, copies and synchronises for
+// it.  Declare every array once, in elements of its type -- in() an input, out() scratch or an output, workspace()
+// the bytes a *_workspace_bytes query reports -- which records offsets only; stage() reserves their sum and enqueues
+// the copies of the inputs on the null stream; operator[] then gives the device pointers; copy_back() enqueues a D2H
+// copy and finish() waits for the stream.  Every slice is bounded by what this call declared, whatever size the arena
+// has grown to.  From stage() on work may be in flight: the destructor drains the null stream on every return that
+// did not reach finish(), before the arena lock (the first member, released last) is dropped -- the StreamDrain rule.
+class StagedCall {
+public:
+    template <typename T>
+    struct Slice {
+        size_t at = 0, count = 0;
+    };
+    StagedCall() = default;
+    StagedCall(const StagedCall&) = delete;
+    StagedCall& operator=(const StagedCall&) = delete;
+    ~StagedCall() {
+        if (in_flight_) (void)hipStreamSynchronize(nullptr);
+    }
+    // `count` elements on the device, the first `copied` of them from `host` (which may be NULL: an optional input)
+    template <typename T>
+    Slice<T> in(const void* host, size_t count, size_t copied) {
+        const Slice<T> s = out<T>(count);
+        if (host && copied) inputs_.push_back({s.at, host, sizeof(T)*std::min(copied, count)});
+        return s;
+    }
+    template <typename T>
+    Slice<T> in(const void* host, size_t count) { return in<T>(host, count, count); }
+    template <typename T>
+    Slice<T> out(size_t count) { return {put(sizeof(T)*count), count}; }
+    // never empty: a callee given zero bytes still gets a pointer of its own
+    Slice<unsigned char> workspace(size_t bytes) { return {put(bytes ? bytes : 1), bytes}; }
+    int stage() {
+        if (int rc = arena_reserve(total_, &base_)) return rc;
+        in_flight_ = true;
+        for (const Input& i : inputs_)
+            FFK_HIP(hipMemcpyAsync(static_cast<unsigned char*>(base_) + i.at, i.host, i.bytes, hipMemcpyHostToDevice,
+                                   nullptr));
+        return FFK_OK;
+    }
+    // NULL before stage(), and for a slice that does not lie inside what this call declared
+    template <typename T>
+    T* operator[](Slice<T> s) const {
+        if (!base_ || s.at + sizeof(T)*s.count > total_) return nullptr;
+        return reinterpret_cast<T*>(static_cast<unsigned char*>(base_) + s.at);
+    }
+    // a declared workspace for a callee that slices it itself
+    Bump bump(Slice<unsigned char> s) const { return Bump((*this)[s], (*this)[s] ? s.count : 0); }
+    int d2h(void* host, const void* device, size_t bytes) {
+        FFK_HIP(hipMemcpyAsync(host, device, bytes, hipMemcpyDeviceToHost, nullptr));
+        return FFK_OK;
+    }
+    template <typename T>
+    int copy_back(void* host, Slice<T> s) {
+        FFK_REQUIRE((*this)[s], "internal: arena too small");
+        return d2h(host, (*this)[s], sizeof(T)*s.count);
+    }
+    int finish() {
+        in_flight_ = false;      // drained below, or the stream is in an error state that no second wait would mend
+        FFK_HIP(hipStreamSynchronize(nullptr));
+        return FFK_OK;
+    }
+    // ... for the entry points that report the kernels' fault word
+    int finish_with_fault_status() {
+        if (int rc = finish()) return rc;
+        return kernel_fault_status();
+    }
+
+private:
+    struct Input {
+        size_t at;
+        const void* host;
+        size_t bytes;
+    };
+    size_t put(size_t bytes) {
+        const size_t at = total_;
+        total_ += align_up(bytes);
+        return at;
+    }
+    std::lock_guard<std::mutex> lock_{g_arena.mu};
+    std::vector<Input> inputs_;
+    size_t total_ = 0;
+    void* base_ = nullptr;
+    bool in_flight_ = false;
+};
+
+// the nine arrays that describe a diagonalised pulse and its noise, as every entry point that starts from them stages
+// them (complex arrays as pairs of doubles, like the C ABI); basis may be NULL
+struct PulseSlices {
+    StagedCall::Slice<double> eigvals, eigvecs, propagators, omega, basis, n_opers, n_coeffs, dt, t;
+};
+inline PulseSlices stage_pulse(StagedCall& c, const double* eigvals, const double* eigvecs, const double* propagators,
+                               const double* omega, int W, const double* basis, int N, const double* n_opers, int A,
+                               const double* n_coeffs, const double* dt, const double* t, int G, int d) {
+    const size_t dd = size_t(d)*d;
+    PulseSlices p;
+    p.eigvals = c.in<double>(eigvals, size_t(G)*d);
+    p.eigvecs = c.in<double>(eigvecs, 2*size_t(G)*dd);
+    p.propagators = c.in<double>(propagators, 2*size_t(G + 1)*dd);
+    p.omega = c.in<double>(omega, W);
+    p.basis = c.in<double>(basis, 2*size_t(N)*dd);
+    p.n_opers = c.in<double>(n_opers, 2*size_t(A)*dd);
+    p.n_coeffs = c.in<double>(n_coeffs, size_t(A)*G);
+    p.dt = c.in<double>(dt, G);
+    p.t = c.in<double>(t, size_t(G) + 1);
+    return p;
+}
+
+// The spectrum of an infidelity integral as the kernels read it: `rows` rows of W c128 values (one for all selected
+// noise operators, one each, or one per pair), and the `n_out` integrals it gives per pulse.
+struct SpectrumShape {
+    size_t rows = 0, n_out = 0;
+};
+inline SpectrumShape spectrum_shape(int s_ndim, int n_idx) {
+    return {s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx),
+            s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx)};
+}
 
 // --- workspace layouts ------------------------------------------------------------------------
 size_t ctrl_ws_bytes(int W, int N, int A, int G, int d, int chunks);

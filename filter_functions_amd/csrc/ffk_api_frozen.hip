@@ -20,84 +20,39 @@ static int second_order_impl(const double* eigvals, const double* eigvecs,
                 "NULL argument");
     FFK_REQUIRE(filter_function_2 || frequency_shifts, "no output requested");
     FFK_REQUIRE(size_t(A)*N <= 65535, "A*N = %zu too large", size_t(A)*N);
-    size_t nS = 0, nout = 0;
-    int srows = 0;
     if (frequency_shifts) {
         FFK_REQUIRE(spectrum && idx, "NULL argument");
         FFK_REQUIRE(s_ndim >= 1 && s_ndim <= 3, "Expected spectrum to have < 4 dimensions, not %d", s_ndim);
         FFK_REQUIRE(n_idx >= 1, "empty axis");
         for (int i = 0; i < n_idx; ++i)
             FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "noise operator index %d out of range [0, %d)", idx[i], A);
-        srows = s_ndim == 1 ? 1 : (s_ndim == 2 ? n_idx : n_idx*n_idx);
-        nS = 16*size_t(W)*srows;
-        nout = size_t(n_idx)*(s_ndim == 3 ? n_idx : 1)*N*N;
     }
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t dd = size_t(d)*d;
-    const size_t nF = size_t(A)*A*N*N*W;
-    const size_t wsb = ffk::second_order_workspace_bytes(G, A, N, d);
-    size_t total = 0;
-    total += align_up(8*size_t(G)*d) + align_up(16*size_t(G)*dd) + align_up(16*size_t(G + 1)*dd);
-    total += align_up(8*size_t(W)) + align_up(16*size_t(N)*dd) + align_up(16*size_t(A)*dd);
-    total += align_up(8*size_t(A)*G) + align_up(8*size_t(G)) + align_up(8*size_t(G + 1));
-    total += align_up(8*size_t(G)*ffk::seg_stride(d)) + align_up(16*size_t(G)*dd) +
-             align_up(16*size_t(G)*(1 + A)*dd);
-    total += align_up(16*size_t(A)*G*dd) + align_up(16*size_t(G)*dd) + align_up(16*size_t(G)*N*dd);
-    total += wsb + align_up(16*nF);
-    total += 2*align_up(nS) + align_up(4*size_t(n_idx > 0 ? n_idx : 1)) + align_up(8*nout);
-    void* base;
-    if (int rc = arena_reserve(total, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dD = a.take<double>(size_t(G)*d);
-    cplx* dV = a.take<cplx>(size_t(G)*dd);
-    cplx* dQ = a.take<cplx>(size_t(G + 1)*dd);
-    double* dom = a.take<double>(W);
-    cplx* dbasis = a.take<cplx>(size_t(N)*dd);
-    cplx* dnop = a.take<cplx>(size_t(A)*dd);
-    double* dnc = a.take<double>(size_t(A)*G);
-    double* ddt = a.take<double>(G);
-    double* dtt = a.take<double>(G + 1);
-    double* segtab = a.take<double>(size_t(G)*ffk::seg_stride(d));
-    cplx* Tc = a.take<cplx>(size_t(G)*dd);
-    cplx* ops = a.take<cplx>(size_t(G)*(1 + A)*dd);
-    cplx* dnt = a.take<cplx>(size_t(A)*G*dd);
-    cplx* dep = a.take<cplx>(size_t(G)*dd);
-    cplx* dbt = a.take<cplx>(size_t(G)*N*dd);
-    void* ws = a.take<unsigned char>(wsb);
-    cplx* dF = a.take<cplx>(nF);
-    cplx* dS = frequency_shifts ? a.take<cplx>(nS/16) : nullptr;
-    cplx* dscale = frequency_shifts ? a.take<cplx>(nS/16) : nullptr;
-    int32_t* didx = frequency_shifts ? a.take<int32_t>(n_idx) : nullptr;
-    double* dout = frequency_shifts ? a.take<double>(nout) : nullptr;
-    FFK_REQUIRE(dF && (!frequency_shifts || dout) && a.used <= g_arena.size,
-                "internal: arena too small");
-    auto h2d = [](void* dst, const void* src, size_t n) {
-        return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, nullptr);
-    };
-    FFK_HIP(h2d(dD, eigvals, 8*size_t(G)*d));
-    FFK_HIP(h2d(dV, eigvecs, 16*size_t(G)*dd));
-    FFK_HIP(h2d(dQ, propagators, 16*size_t(G + 1)*dd));
-    FFK_HIP(h2d(dom, omega, 8*size_t(W)));
-    FFK_HIP(h2d(dbasis, basis, 16*size_t(N)*dd));
-    FFK_HIP(h2d(dnop, n_opers, 16*size_t(A)*dd));
-    FFK_HIP(h2d(dnc, n_coeffs, 8*size_t(A)*G));
-    FFK_HIP(h2d(ddt, dt, 8*size_t(G)));
-    FFK_HIP(h2d(dtt, t, 8*size_t(G + 1)));
-    FFK_HIP(ffk::launch_prologue(dD, dV, dQ, dnop, dnc, ddt, dtt, G, d, A, segtab, Tc, ops, dnt, dep, nullptr));
-    FFK_HIP(ffk::launch_basis_transformed(Tc, dbasis, G, N, d, dbt, nullptr));
-    FFK_HIP(ffk::launch_second_order_filter_function(dom, W, dD, ddt, dtt, dnt, dbt, G, d, A, N, dF, ws,
-                                                     nullptr));
+    StagedCall c;
+    const SpectrumShape sh = frequency_shifts ? spectrum_shape(s_ndim, n_idx) : SpectrumShape{};
+    const size_t wsb = ffk_second_order_workspace_bytes(W, N, A, G, d);
+    const size_t swsb = frequency_shifts ? ffk_frequency_shifts_workspace_bytes(W, n_idx, s_ndim) : 0;
+    const PulseSlices p = stage_pulse(c, eigvals, eigvecs, propagators, omega, W, basis, N, n_opers, A, n_coeffs, dt,
+                                      t, G, d);
+    const auto F = c.out<double>(2*size_t(A)*A*N*N*W);
+    const auto ws = c.workspace(wsb);
+    const auto S = c.in<double>(spectrum, 2*size_t(W)*sh.rows);
+    const auto didx = c.in<int32_t>(idx, frequency_shifts ? n_idx : 0);
+    const auto shifts = c.out<double>(sh.n_out*N*N);
+    const auto sws = c.out<unsigned char>(swsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_second_order_filter_function_dev(c[p.eigvals], c[p.eigvecs], c[p.propagators], c[p.omega], W,
+                                                      c[p.basis], N, c[p.n_opers], A, c[p.n_coeffs], c[p.dt], c[p.t],
+                                                      G, d, c[F], c[ws], wsb, nullptr))
+        return rc;
     if (frequency_shifts) {
-        FFK_HIP(h2d(dS, spectrum, nS));
-        FFK_HIP(h2d(didx, idx, 4*size_t(n_idx)));
-        FFK_HIP(ffk::launch_spectral_weights(dS, srows, W, dom, W, 0, dscale, nullptr));
-        FFK_HIP(ffk::launch_frequency_shifts(dF, A, N, W, dscale, s_ndim, didx, n_idx, dout, nullptr));
-        FFK_HIP(hipMemcpyAsync(frequency_shifts, dout, 8*nout, hipMemcpyDeviceToHost, nullptr));
+        if (int rc = ffk_frequency_shifts_shard_dev(c[F], A, N, W, c[S], s_ndim, c[p.omega], W, 0, c[didx], n_idx,
+                                                    c[shifts], c[sws], swsb, nullptr))
+            return rc;
+        if (int rc = c.copy_back(frequency_shifts, shifts)) return rc;
     }
     if (filter_function_2)
-        FFK_HIP(hipMemcpyAsync(filter_function_2, dF, 16*nF, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+        if (int rc = c.copy_back(filter_function_2, F)) return rc;
+    return c.finish();
 }
 
 int ffk_second_order_filter_function(const double* eigvals, const double* eigvecs,
@@ -128,30 +83,17 @@ int ffk_second_order_filter_function_from_atomic(const double* filter_function_a
     FFK_REQUIRE(filter_function_atomic && control_matrix_step && filter_function_2, "NULL argument");
     FFK_REQUIRE(G >= 1 && A >= 1 && N >= 1 && W >= 1, "empty axis: G=%d A=%d N=%d W=%d", G, A, N, W);
     FFK_REQUIRE(G == 1 || propagators_liouville, "NULL argument");
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nF = 16*size_t(A)*A*N*N*W, nR = 16*size_t(G)*A*N*W;
-    const size_t nL = 8*size_t(G > 1 ? G - 1 : 1)*N*N;
-    const size_t wsb = ffk::second_order_from_atomic_workspace_bytes(G, A, N, W);
-    void* base;
-    if (int rc = arena_reserve(align_up(size_t(G)*nF) + align_up(nR) + align_up(nL) + wsb +
-                                   align_up(nF), &base))
-        return rc;
-    Bump a(base, g_arena.size);
-    cplx* dFa = a.take<cplx>(size_t(G)*nF/16);
-    cplx* dR = a.take<cplx>(nR/16);
-    double* dL = a.take<double>(nL/8);
-    void* ws = a.take<unsigned char>(wsb);
-    cplx* dout = a.take<cplx>(nF/16);
-    FFK_REQUIRE(dout, "internal: arena too small");
-    FFK_HIP(hipMemcpyAsync(dFa, filter_function_atomic, size_t(G)*nF, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix_step, nR, hipMemcpyHostToDevice, nullptr));
-    if (G > 1)
-        FFK_HIP(hipMemcpyAsync(dL, propagators_liouville, 8*size_t(G - 1)*N*N, hipMemcpyHostToDevice,
-                               nullptr));
-    FFK_HIP(ffk::launch_second_order_from_atomic(dFa, dR, dL, G, A, N, W, dout, ws, nullptr));
-    FFK_HIP(hipMemcpyAsync(filter_function_2, dout, nF, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    StagedCall c;
+    const size_t nl = G > 1 ? G - 1 : 1;
+    const auto Fa = c.in<cplx>(filter_function_atomic, size_t(G)*A*A*N*N*W);
+    const auto R = c.in<cplx>(control_matrix_step, size_t(G)*A*N*W);
+    const auto L = c.in<double>(propagators_liouville, nl*N*N, size_t(G - 1)*N*N);
+    const auto ws = c.workspace(ffk::second_order_from_atomic_workspace_bytes(G, A, N, W));
+    const auto out = c.out<cplx>(size_t(A)*A*N*N*W);
+    if (int rc = c.stage()) return rc;
+    FFK_HIP(ffk::launch_second_order_from_atomic(c[Fa], c[R], c[L], G, A, N, W, c[out], c[ws], nullptr));
+    if (int rc = c.copy_back(filter_function_2, out)) return rc;
+    return c.finish();
 }
 
 int ffk_frequency_shifts(const double* filter_function_2, int A, int N, int W, const double* spectrum,
@@ -162,32 +104,21 @@ int ffk_frequency_shifts(const double* filter_function_2, int A, int N, int W, c
     FFK_REQUIRE(A >= 1 && N >= 1 && W >= 1 && n_idx >= 1, "empty axis");
     for (int i = 0; i < n_idx; ++i)
         FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "noise operator index %d out of range [0, %d)", idx[i], A);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nF = 16*size_t(A)*A*N*N*W;
-    const int rows = s_ndim == 1 ? 1 : (s_ndim == 2 ? n_idx : n_idx*n_idx);
-    const size_t nS = 16*size_t(W)*rows;
-    const size_t nout = size_t(n_idx)*(s_ndim == 3 ? n_idx : 1)*N*N;
-    void* base;
-    if (int rc = arena_reserve(align_up(nF) + 2*align_up(nS) + align_up(8*size_t(W)) +
-                                   align_up(4*size_t(n_idx)) + align_up(8*nout), &base))
+    StagedCall c;
+    const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
+    const size_t wsb = ffk_frequency_shifts_workspace_bytes(W, n_idx, s_ndim);
+    const auto F = c.in<double>(filter_function_2, 2*size_t(A)*A*N*N*W);
+    const auto S = c.in<double>(spectrum, 2*size_t(W)*sh.rows);
+    const auto om = c.in<double>(omega, W);
+    const auto didx = c.in<int32_t>(idx, n_idx);
+    const auto out = c.out<double>(sh.n_out*N*N);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_frequency_shifts_shard_dev(c[F], A, N, W, c[S], s_ndim, c[om], W, 0, c[didx], n_idx, c[out],
+                                                c[ws], wsb, nullptr))
         return rc;
-    Bump a(base, g_arena.size);
-    cplx* dF = a.take<cplx>(nF/16);
-    cplx* dS = a.take<cplx>(nS/16);
-    cplx* dscale = a.take<cplx>(nS/16);
-    double* dom = a.take<double>(W);
-    int32_t* didx = a.take<int32_t>(n_idx);
-    double* dout = a.take<double>(nout);
-    FFK_REQUIRE(dout, "internal: arena too small");
-    FFK_HIP(hipMemcpyAsync(dF, filter_function_2, nF, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dS, spectrum, nS, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dom, omega, 8*size_t(W), hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(didx, idx, 4*size_t(n_idx), hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(ffk::launch_spectral_weights(dS, rows, W, dom, W, 0, dscale, nullptr));
-    FFK_HIP(ffk::launch_frequency_shifts(dF, A, N, W, dscale, s_ndim, didx, n_idx, dout, nullptr));
-    FFK_HIP(hipMemcpyAsync(frequency_shifts, dout, 8*nout, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    if (int rc = c.copy_back(frequency_shifts, out)) return rc;
+    return c.finish();
 }
 
 int ffk_cumulant_function_second_order(const double* frequency_shifts, int batch, int N, int d,
@@ -195,26 +126,17 @@ int ffk_cumulant_function_second_order(const double* frequency_shifts, int batch
     FFK_REQUIRE(frequency_shifts && basis && cumulant_function, "NULL argument");
     FFK_REQUIRE(batch >= 1 && N >= 1, "empty axis");
     FFK_REQUIRE(d_templated_ok(d), "dimension %d outside [2, %d]", d, FFK_MAX_D_TEMPLATED);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nG = 8*size_t(batch)*N*N;
-    const size_t nB = 16*size_t(N)*d*d;
-    const size_t wsb = ffk::cumulant_second_order_workspace_bytes(batch, N, d);
-    void* base;
-    if (int rc = arena_reserve(2*align_up(nG) + align_up(nB) + align_up(wsb), &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dD = a.take<double>(nG/8);
-    double* dK = a.take<double>(nG/8);
-    double* dB = a.take<double>(nB/8);
-    void* ws = a.take<unsigned char>(wsb);
-    FFK_REQUIRE(ws, "internal: arena too small");
-    FFK_HIP(hipMemcpyAsync(dD, frequency_shifts, nG, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dK, cumulant_function, nG, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dB, basis, nB, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(ffk::launch_cumulant_second_order(dD, batch, N, d, reinterpret_cast<const cplx*>(dB), dK, ws,
-                                              nullptr));
-    FFK_HIP(hipMemcpyAsync(cumulant_function, dK, nG, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    StagedCall c;
+    const size_t wsb = ffk_cumulant_function_second_order_workspace_bytes(batch, N, d);
+    const auto D = c.in<double>(frequency_shifts, size_t(batch)*N*N);
+    const auto K = c.in<double>(cumulant_function, size_t(batch)*N*N);      // added to in place
+    const auto B = c.in<double>(basis, 2*size_t(N)*d*d);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_cumulant_function_second_order_dev(c[D], batch, N, d, c[B], c[K], c[ws], wsb, nullptr))
+        return rc;
+    if (int rc = c.copy_back(cumulant_function, K)) return rc;
+    return c.finish();
 }
 
 size_t ffk_second_order_workspace_bytes(int W, int N, int A, int G, int d) {
@@ -264,7 +186,7 @@ int ffk_second_order_filter_function_dev(const double* eigvals, const double* ei
 
 size_t ffk_frequency_shifts_workspace_bytes(int W, int n_idx, int s_ndim) {
     if (W < 1 || n_idx < 1 || s_ndim < 1 || s_ndim > 3) return 0;
-    return align_up(16*size_t(W)*(s_ndim == 1 ? 1 : (s_ndim == 2 ? n_idx : size_t(n_idx)*n_idx)));
+    return align_up(16*size_t(W)*spectrum_shape(s_ndim, n_idx).rows);
 }
 
 int ffk_frequency_shifts_shard_dev(const double* filter_function_2, int A, int N, int W_block,
@@ -280,7 +202,7 @@ int ffk_frequency_shifts_shard_dev(const double* filter_function_2, int A, int N
                 w_offset, w_offset + W_block, W);
     FFK_REQUIRE(workspace_bytes >= ffk_frequency_shifts_workspace_bytes(W_block, n_idx, s_ndim),
                 "workspace too small");
-    const int rows = s_ndim == 1 ? 1 : (s_ndim == 2 ? n_idx : n_idx*n_idx);
+    const int rows = static_cast<int>(spectrum_shape(s_ndim, n_idx).rows);
     hipStream_t st = static_cast<hipStream_t>(stream);
     cplx* scale = static_cast<cplx*>(workspace);
     FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(spectrum), rows, W_block, omega, W,
@@ -312,6 +234,59 @@ int ffk_cumulant_function_second_order_dev(const double* frequency_shifts, int b
 // ---------------------------------------------------------------------------------------------
 // gradient: derivative of the filter function / infidelity w.r.t. the control amplitudes
 // ---------------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// What every gradient starts from, on stream `st` with its temporaries from `ws`: Bbar, T of the noise operators and
+// Abar of the control operators (unit coefficients), the Hilbert-space steps of the interaction-picture noise
+// operators, one chunk per segment, and their running sums.
+struct GradientFront {
+    cplx *ops, *abar, *E, *Y;
+};
+size_t gradient_front_bytes(int W, int A, int H, int G, int d) {
+    const size_t dd = size_t(d)*d;
+    const int HA = H > A ? H : A;
+    size_t b = 0;
+    b += 2*(align_up(8*size_t(G)*ffk::seg_stride(d)) + align_up(16*size_t(G)*dd) +
+            align_up(16*size_t(G)*(1 + HA)*dd));                                   // segtab, Tc, ops (x2)
+    b += align_up(16*size_t(A)*G*dd) + align_up(16*size_t(H)*G*dd) + 2*align_up(16*size_t(G)*dd);
+    b += align_up(16*size_t(H)*G*dd);                                              // E
+    b += align_up(16*size_t(G)*A*dd*W);                                            // Y steps / Ycum
+    return b;
+}
+int gradient_front(const double* eigvals, const double* eigvecs, const double* propagators, const double* omega,
+                   int W, const double* n_opers, int A, const double* n_coeffs, const double* c_opers, int H,
+                   const double* dt, const double* t, int G, int d, Bump& ws, hipStream_t st, GradientFront* out) {
+    const size_t dd = size_t(d)*d;
+    const int HA = H > A ? H : A;
+    double* segtab = ws.take<double>(size_t(G)*ffk::seg_stride(d));
+    cplx* Tc = ws.take<cplx>(size_t(G)*dd);
+    cplx* ops = ws.take<cplx>(size_t(G)*(1 + HA)*dd);
+    double* segtab2 = ws.take<double>(size_t(G)*ffk::seg_stride(d));
+    cplx* Tc2 = ws.take<cplx>(size_t(G)*dd);
+    cplx* ops2 = ws.take<cplx>(size_t(G)*(1 + HA)*dd);
+    cplx* dnt = ws.take<cplx>(size_t(A)*G*dd);
+    cplx* dabar = ws.take<cplx>(size_t(H)*G*dd);
+    cplx* dep = ws.take<cplx>(size_t(G)*dd);
+    cplx* dep2 = ws.take<cplx>(size_t(G)*dd);
+    cplx* dE = ws.take<cplx>(size_t(H)*G*dd);
+    cplx* Y = ws.take<cplx>(size_t(G)*A*dd*W);
+    FFK_REQUIRE(segtab && Tc && ops && segtab2 && Tc2 && ops2 && dnt && dabar && dep && dep2 && dE && Y,
+                "internal: workspace too small");
+    const cplx* V = reinterpret_cast<const cplx*>(eigvecs);
+    const cplx* Q = reinterpret_cast<const cplx*>(propagators);
+    FFK_HIP(ffk::launch_prologue(eigvals, V, Q, reinterpret_cast<const cplx*>(n_opers), n_coeffs, dt, t, G,
+                                 d, A, segtab, Tc, ops, dnt, dep, st));
+    FFK_HIP(ffk::launch_prologue(eigvals, V, Q, reinterpret_cast<const cplx*>(c_opers), nullptr, dt, t, G,
+                                 d, H, segtab2, Tc2, ops2, dabar, dep2, st));
+    ffk::AccumGeometry geo = ffk::accumulate_geometry(W, A, G, d, G);
+    FFK_HIP(ffk::launch_accumulate(omega, W, segtab, ops, G, d, A, geo, Y, st));
+    FFK_HIP(ffk::launch_segment_prefix_sum(Y, G, size_t(A)*dd*W, st));
+    *out = {ops, dabar, dE, Y};
+    return FFK_OK;
+}
+}  // namespace
+extern "C" {
+
 int ffk_filter_function_derivative(const double* eigvals, const double* eigvecs,
                                    const double* propagators, const double* omega, int W,
                                    const double* n_opers, int A, const double* n_coeffs,
@@ -328,87 +303,28 @@ int ffk_filter_function_derivative(const double* eigvals, const double* eigvecs,
     FFK_REQUIRE(!infidelity_derivative || (spectrum && (s_ndim == 1 || s_ndim == 2)),
                 "infidelity derivative needs a spectrum of shape (W,) or (A, W)");
     FFK_REQUIRE(size_t(G)*A <= 65535, "G*A = %zu too large", size_t(G)*A);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t dd = size_t(d)*d;
-    const size_t nY = size_t(G)*A*dd*W, nF = size_t(A)*G*H*W;
-    const int srows = s_ndim == 2 ? A : 1;
-    const size_t nS = infidelity_derivative ? 16*size_t(W)*srows : 0;
-    const int HA = H > A ? H : A;
-    size_t total = 0;
-    total += align_up(8*size_t(G)*d) + align_up(16*size_t(G)*dd) + align_up(16*size_t(G + 1)*dd);
-    total += align_up(8*size_t(W)) + align_up(16*size_t(A)*dd) + align_up(16*size_t(H)*dd);
-    total += align_up(8*size_t(A)*G) + align_up(8*size_t(H)*G) + align_up(8*size_t(G)) + align_up(8*size_t(G + 1));
-    total += align_up(8*size_t(A)*H*G);
-    total += 2*(align_up(8*size_t(G)*ffk::seg_stride(d)) + align_up(16*size_t(G)*dd) +
-                align_up(16*size_t(G)*(1 + HA)*dd));
-    total += align_up(16*size_t(A)*G*dd) + align_up(16*size_t(H)*G*dd) + 2*align_up(16*size_t(G)*dd);
-    total += align_up(16*size_t(H)*G*dd);                                       // E
-    total += align_up(16*nY) + align_up(8*nF) + 2*align_up(nS) + align_up(8*size_t(A)*G*H);
-    void* base;
-    if (int rc = arena_reserve(total, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dD = a.take<double>(size_t(G)*d);
-    cplx* dV = a.take<cplx>(size_t(G)*dd);
-    cplx* dQ = a.take<cplx>(size_t(G + 1)*dd);
-    double* dom = a.take<double>(W);
-    cplx* dnop = a.take<cplx>(size_t(A)*dd);
-    cplx* dcop = a.take<cplx>(size_t(H)*dd);
-    double* dnc = a.take<double>(size_t(A)*G);
-    double* ddt = a.take<double>(G);
-    double* dtt = a.take<double>(G + 1);
-    double* dratio = a.take<double>(size_t(A)*H*G);
-    double* segtab = a.take<double>(size_t(G)*ffk::seg_stride(d));
-    cplx* Tc = a.take<cplx>(size_t(G)*dd);
-    cplx* ops = a.take<cplx>(size_t(G)*(1 + HA)*dd);
-    double* segtab2 = a.take<double>(size_t(G)*ffk::seg_stride(d));
-    cplx* Tc2 = a.take<cplx>(size_t(G)*dd);
-    cplx* ops2 = a.take<cplx>(size_t(G)*(1 + HA)*dd);
-    cplx* dnt = a.take<cplx>(size_t(A)*G*dd);
-    cplx* dabar = a.take<cplx>(size_t(H)*G*dd);
-    cplx* dep = a.take<cplx>(size_t(G)*dd);
-    cplx* dep2 = a.take<cplx>(size_t(G)*dd);
-    cplx* dE = a.take<cplx>(size_t(H)*G*dd);
-    cplx* Y = a.take<cplx>(nY);
-    double* dF = a.take<double>(nF);
-    cplx* dS = nS ? a.take<cplx>(nS/16) : nullptr;
-    cplx* dscale = nS ? a.take<cplx>(nS/16) : nullptr;
-    double* dI = a.take<double>(size_t(A)*G*H);
-    FFK_REQUIRE(dI && a.used <= g_arena.size, "internal: arena too small");
-    auto h2d = [](void* dst, const void* src, size_t n) {
-        return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, nullptr);
-    };
-    FFK_HIP(h2d(dD, eigvals, 8*size_t(G)*d));
-    FFK_HIP(h2d(dV, eigvecs, 16*size_t(G)*dd));
-    FFK_HIP(h2d(dQ, propagators, 16*size_t(G + 1)*dd));
-    FFK_HIP(h2d(dom, omega, 8*size_t(W)));
-    FFK_HIP(h2d(dnop, n_opers, 16*size_t(A)*dd));
-    FFK_HIP(h2d(dcop, c_opers, 16*size_t(H)*dd));
-    FFK_HIP(h2d(dnc, n_coeffs, 8*size_t(A)*G));
-    FFK_HIP(h2d(ddt, dt, 8*size_t(G)));
-    FFK_HIP(h2d(dtt, t, 8*size_t(G + 1)));
-    if (n_coeffs_ratio) FFK_HIP(h2d(dratio, n_coeffs_ratio, 8*size_t(A)*H*G));
-    // Bbar, T (noise operators) and Abar (control operators, unit coefficients)
-    FFK_HIP(ffk::launch_prologue(dD, dV, dQ, dnop, dnc, ddt, dtt, G, d, A, segtab, Tc, ops, dnt, dep, nullptr));
-    FFK_HIP(ffk::launch_prologue(dD, dV, dQ, dcop, nullptr, ddt, dtt, G, d, H, segtab2, Tc2, ops2, dabar,
-                                 dep2, nullptr));
-    // Hilbert-space steps of the interaction-picture noise operators, one chunk per segment, then
-    // their running sums
-    ffk::AccumGeometry geo = ffk::accumulate_geometry(W, A, G, d, G);
-    FFK_HIP(ffk::launch_accumulate(dom, W, segtab, ops, G, d, A, geo, Y, nullptr));
-    FFK_HIP(ffk::launch_segment_prefix_sum(Y, G, size_t(A)*dd*W, nullptr));
-    FFK_HIP(ffk::launch_filter_function_derivative(dom, W, dD, ddt, dtt, ops, dabar, Y,
-                                                   n_coeffs_ratio ? dratio : nullptr, G, d, A, H, dE, dF,
-                                                   nullptr));
-    if (infidelity_derivative) {
-        FFK_HIP(h2d(dS, spectrum, nS));
-        FFK_HIP(ffk::launch_spectral_weights(dS, srows, W, dom, W, 0, dscale, nullptr));
-        FFK_HIP(ffk::launch_infidelity_derivative(dF, A, G, H, W, dscale, s_ndim, d, dI, nullptr));
-        FFK_HIP(hipMemcpyAsync(infidelity_derivative, dI, 8*size_t(A)*G*H, hipMemcpyDeviceToHost, nullptr));
-    }
+    StagedCall c;
+    const bool want_dI = infidelity_derivative != nullptr;
+    const size_t wsb = ffk_filter_function_derivative_workspace_bytes(W, A, H, G, d);
+    const PulseSlices p = stage_pulse(c, eigvals, eigvecs, propagators, omega, W, nullptr, 0, n_opers, A, n_coeffs,
+                                      dt, t, G, d);
+    const auto cop = c.in<double>(c_opers, 2*size_t(H)*d*d);
+    const auto ratio = c.in<double>(n_coeffs_ratio, size_t(A)*H*G);
+    const auto S = c.in<double>(spectrum, want_dI ? 2*size_t(W)*(s_ndim == 2 ? A : 1) : 0);
+    const auto dF = c.out<double>(size_t(A)*G*H*W);      // the device pass always writes it
+    const auto dI = c.out<double>(size_t(A)*G*H);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_filter_function_derivative_shard_dev(
+            c[p.eigvals], c[p.eigvecs], c[p.propagators], c[p.omega], W, c[p.n_opers], A, c[p.n_coeffs], c[cop], H,
+            n_coeffs_ratio ? c[ratio] : nullptr, c[p.dt], c[p.t], G, d, want_dI ? c[S] : nullptr, s_ndim, c[p.omega],
+            W, 0, c[dF], want_dI ? c[dI] : nullptr, c[ws], wsb, nullptr))
+        return rc;
+    if (want_dI)
+        if (int rc = c.copy_back(infidelity_derivative, dI)) return rc;
     if (filter_function_derivative)
-        FFK_HIP(hipMemcpyAsync(filter_function_derivative, dF, 8*nF, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return kernel_fault_status();
+        if (int rc = c.copy_back(filter_function_derivative, dF)) return rc;
+    return c.finish_with_fault_status();
 }
 
 int ffk_control_matrix_derivative(const double* eigvals, const double* eigvecs, const double* propagators,
@@ -423,75 +339,25 @@ int ffk_control_matrix_derivative(const double* eigvals, const double* eigvecs, 
     FFK_REQUIRE(eigvals && eigvecs && propagators && omega && basis && n_opers && n_coeffs && c_opers && dt &&
                     t && control_matrix_derivative, "NULL argument");
     FFK_REQUIRE(size_t(G)*A <= 65535, "G*A = %zu too large", size_t(G)*A);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t dd = size_t(d)*d;
-    const size_t nY = size_t(G)*A*dd*W, nR = size_t(H)*W*G*A*N;
-    const int HA = H > A ? H : A;
-    size_t total = 0;
-    total += align_up(8*size_t(G)*d) + align_up(16*size_t(G)*dd) + align_up(16*size_t(G + 1)*dd);
-    total += align_up(8*size_t(W)) + align_up(16*size_t(A)*dd) + align_up(16*size_t(H)*dd);
-    total += align_up(16*size_t(N)*dd);
-    total += align_up(8*size_t(A)*G) + align_up(8*size_t(G)) + align_up(8*size_t(G + 1));
-    total += align_up(8*size_t(A)*H*G);
-    total += 2*(align_up(8*size_t(G)*ffk::seg_stride(d)) + align_up(16*size_t(G)*dd) +
-                align_up(16*size_t(G)*(1 + HA)*dd));
-    total += align_up(16*size_t(A)*G*dd) + align_up(16*size_t(H)*G*dd) + 2*align_up(16*size_t(G)*dd);
-    total += align_up(16*size_t(H)*G*dd);
-    total += align_up(16*nY) + align_up(16*nR);
-    void* base;
-    if (int rc = arena_reserve(total, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dD = a.take<double>(size_t(G)*d);
-    cplx* dV = a.take<cplx>(size_t(G)*dd);
-    cplx* dQ = a.take<cplx>(size_t(G + 1)*dd);
-    double* dom = a.take<double>(W);
-    cplx* dnop = a.take<cplx>(size_t(A)*dd);
-    cplx* dcop = a.take<cplx>(size_t(H)*dd);
-    cplx* dbasis = a.take<cplx>(size_t(N)*dd);
-    double* dnc = a.take<double>(size_t(A)*G);
-    double* ddt = a.take<double>(G);
-    double* dtt = a.take<double>(G + 1);
-    double* dratio = a.take<double>(size_t(A)*H*G);
-    double* segtab = a.take<double>(size_t(G)*ffk::seg_stride(d));
-    cplx* Tc = a.take<cplx>(size_t(G)*dd);
-    cplx* ops = a.take<cplx>(size_t(G)*(1 + HA)*dd);
-    double* segtab2 = a.take<double>(size_t(G)*ffk::seg_stride(d));
-    cplx* Tc2 = a.take<cplx>(size_t(G)*dd);
-    cplx* ops2 = a.take<cplx>(size_t(G)*(1 + HA)*dd);
-    cplx* dnt = a.take<cplx>(size_t(A)*G*dd);
-    cplx* dabar = a.take<cplx>(size_t(H)*G*dd);
-    cplx* dep = a.take<cplx>(size_t(G)*dd);
-    cplx* dep2 = a.take<cplx>(size_t(G)*dd);
-    cplx* dE = a.take<cplx>(size_t(H)*G*dd);
-    cplx* Y = a.take<cplx>(nY);
-    cplx* dR = a.take<cplx>(nR);
-    FFK_REQUIRE(dR && a.used <= g_arena.size, "internal: arena too small");
-    auto h2d = [](void* dst, const void* src, size_t n) {
-        return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, nullptr);
-    };
-    FFK_HIP(h2d(dD, eigvals, 8*size_t(G)*d));
-    FFK_HIP(h2d(dV, eigvecs, 16*size_t(G)*dd));
-    FFK_HIP(h2d(dQ, propagators, 16*size_t(G + 1)*dd));
-    FFK_HIP(h2d(dom, omega, 8*size_t(W)));
-    FFK_HIP(h2d(dnop, n_opers, 16*size_t(A)*dd));
-    FFK_HIP(h2d(dcop, c_opers, 16*size_t(H)*dd));
-    FFK_HIP(h2d(dbasis, basis, 16*size_t(N)*dd));
-    FFK_HIP(h2d(dnc, n_coeffs, 8*size_t(A)*G));
-    FFK_HIP(h2d(ddt, dt, 8*size_t(G)));
-    FFK_HIP(h2d(dtt, t, 8*size_t(G + 1)));
-    if (n_coeffs_ratio) FFK_HIP(h2d(dratio, n_coeffs_ratio, 8*size_t(A)*H*G));
-    FFK_HIP(ffk::launch_prologue(dD, dV, dQ, dnop, dnc, ddt, dtt, G, d, A, segtab, Tc, ops, dnt, dep, nullptr));
-    FFK_HIP(ffk::launch_prologue(dD, dV, dQ, dcop, nullptr, ddt, dtt, G, d, H, segtab2, Tc2, ops2, dabar,
-                                 dep2, nullptr));
-    ffk::AccumGeometry geo = ffk::accumulate_geometry(W, A, G, d, G);
-    FFK_HIP(ffk::launch_accumulate(dom, W, segtab, ops, G, d, A, geo, Y, nullptr));
-    FFK_HIP(ffk::launch_segment_prefix_sum(Y, G, size_t(A)*dd*W, nullptr));
-    FFK_HIP(ffk::launch_control_matrix_derivative(dom, W, dD, ddt, dtt, ops, dabar, Y,
-                                                  n_coeffs_ratio ? dratio : nullptr, dbasis, N, G, d, A, H,
-                                                  dE, dR, nullptr));
-    FFK_HIP(hipMemcpyAsync(control_matrix_derivative, dR, 16*nR, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return kernel_fault_status();
+    StagedCall c;
+    const PulseSlices p = stage_pulse(c, eigvals, eigvecs, propagators, omega, W, basis, N, n_opers, A, n_coeffs, dt,
+                                      t, G, d);
+    const auto cop = c.in<double>(c_opers, 2*size_t(H)*d*d);
+    const auto ratio = c.in<double>(n_coeffs_ratio, size_t(A)*H*G);
+    const auto R = c.out<cplx>(size_t(H)*W*G*A*N);
+    const auto ws = c.workspace(gradient_front_bytes(W, A, H, G, d));
+    if (int rc = c.stage()) return rc;
+    Bump a = c.bump(ws);
+    GradientFront f;
+    if (int rc = gradient_front(c[p.eigvals], c[p.eigvecs], c[p.propagators], c[p.omega], W, c[p.n_opers], A,
+                                c[p.n_coeffs], c[cop], H, c[p.dt], c[p.t], G, d, a, nullptr, &f))
+        return rc;
+    FFK_HIP(ffk::launch_control_matrix_derivative(c[p.omega], W, c[p.eigvals], c[p.dt], c[p.t], f.ops, f.abar, f.Y,
+                                                  n_coeffs_ratio ? c[ratio] : nullptr,
+                                                  reinterpret_cast<const cplx*>(c[p.basis]), N, G, d, A, H, f.E,
+                                                  c[R], nullptr));
+    if (int rc = c.copy_back(control_matrix_derivative, R)) return rc;
+    return c.finish_with_fault_status();
 }
 
 int ffk_filter_function_derivative_from_control_matrix(const double* control_matrix,
@@ -501,35 +367,19 @@ int ffk_filter_function_derivative_from_control_matrix(const double* control_mat
     FFK_REQUIRE(control_matrix && control_matrix_derivative && filter_function_derivative, "NULL argument");
     FFK_REQUIRE(A >= 1 && N >= 1 && W >= 1 && G >= 1 && H >= 1, "empty axis: A=%d N=%d W=%d G=%d H=%d", A, N,
                 W, G, H);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nR = size_t(A)*N*W, nD = size_t(H)*W*G*A*N, nF = size_t(A)*G*H*W;
-    void* base;
-    if (int rc = arena_reserve(align_up(16*nR) + align_up(16*nD) + align_up(8*nF), &base)) return rc;
-    Bump a(base, g_arena.size);
-    cplx* dR = a.take<cplx>(nR);
-    cplx* dD = a.take<cplx>(nD);
-    double* dF = a.take<double>(nF);
-    FFK_REQUIRE(dF && a.used <= g_arena.size, "internal: arena too small");
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix, 16*nR, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dD, control_matrix_derivative, 16*nD, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(ffk::launch_filter_function_derivative_from_control_matrix(dR, dD, A, N, W, G, H, dF, nullptr));
-    FFK_HIP(hipMemcpyAsync(filter_function_derivative, dF, 8*nF, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    StagedCall c;
+    const auto R = c.in<cplx>(control_matrix, size_t(A)*N*W);
+    const auto D = c.in<cplx>(control_matrix_derivative, size_t(H)*W*G*A*N);
+    const auto F = c.out<double>(size_t(A)*G*H*W);
+    if (int rc = c.stage()) return rc;
+    FFK_HIP(ffk::launch_filter_function_derivative_from_control_matrix(c[R], c[D], A, N, W, G, H, c[F], nullptr));
+    if (int rc = c.copy_back(filter_function_derivative, F)) return rc;
+    return c.finish();
 }
 
 size_t ffk_filter_function_derivative_workspace_bytes(int W, int A, int H, int G, int d) {
     if (W < 1 || A < 1 || H < 1 || G < 1 || d < 2 || d > 8) return 0;
-    const size_t dd = size_t(d)*d;
-    const int HA = H > A ? H : A;
-    size_t b = 0;
-    b += 2*(align_up(8*size_t(G)*ffk::seg_stride(d)) + align_up(16*size_t(G)*dd) +
-            align_up(16*size_t(G)*(1 + HA)*dd));                                   // segtab, Tc, ops (x2)
-    b += align_up(16*size_t(A)*G*dd) + align_up(16*size_t(H)*G*dd) + 2*align_up(16*size_t(G)*dd);
-    b += align_up(16*size_t(H)*G*dd);                                              // E
-    b += align_up(16*size_t(G)*A*dd*W);                                            // Y steps / Ycum
-    b += align_up(16*size_t(W)*A);                                                 // spectral weights
-    return b;
+    return gradient_front_bytes(W, A, H, G, d) + align_up(16*size_t(W)*A);         // + spectral weights
 }
 
 int ffk_filter_function_derivative_shard_dev(const double* eigvals, const double* eigvecs,
@@ -553,35 +403,16 @@ int ffk_filter_function_derivative_shard_dev(const double* eigvals, const double
     FFK_REQUIRE(size_t(G)*A <= 65535, "G*A = %zu too large", size_t(G)*A);
     FFK_REQUIRE(workspace_bytes >= ffk_filter_function_derivative_workspace_bytes(W_block, A, H, G, d),
                 "workspace too small");
-    const size_t dd = size_t(d)*d;
-    const int HA = H > A ? H : A;
     hipStream_t st = static_cast<hipStream_t>(stream);
     Bump a(workspace, workspace_bytes);
-    double* segtab = a.take<double>(size_t(G)*ffk::seg_stride(d));
-    cplx* Tc = a.take<cplx>(size_t(G)*dd);
-    cplx* ops = a.take<cplx>(size_t(G)*(1 + HA)*dd);
-    double* segtab2 = a.take<double>(size_t(G)*ffk::seg_stride(d));
-    cplx* Tc2 = a.take<cplx>(size_t(G)*dd);
-    cplx* ops2 = a.take<cplx>(size_t(G)*(1 + HA)*dd);
-    cplx* dnt = a.take<cplx>(size_t(A)*G*dd);
-    cplx* dabar = a.take<cplx>(size_t(H)*G*dd);
-    cplx* dep = a.take<cplx>(size_t(G)*dd);
-    cplx* dep2 = a.take<cplx>(size_t(G)*dd);
-    cplx* dE = a.take<cplx>(size_t(H)*G*dd);
-    cplx* Y = a.take<cplx>(size_t(G)*A*dd*W_block);
+    GradientFront f;
+    if (int rc = gradient_front(eigvals, eigvecs, propagators, omega_block, W_block, n_opers, A, n_coeffs, c_opers,
+                                H, dt, t, G, d, a, st, &f))
+        return rc;
     cplx* dscale = a.take<cplx>(size_t(W_block)*A);
     FFK_REQUIRE(dscale, "internal: workspace too small");
-    const cplx* V = reinterpret_cast<const cplx*>(eigvecs);
-    const cplx* Q = reinterpret_cast<const cplx*>(propagators);
-    FFK_HIP(ffk::launch_prologue(eigvals, V, Q, reinterpret_cast<const cplx*>(n_opers), n_coeffs, dt, t, G,
-                                 d, A, segtab, Tc, ops, dnt, dep, st));
-    FFK_HIP(ffk::launch_prologue(eigvals, V, Q, reinterpret_cast<const cplx*>(c_opers), nullptr, dt, t, G,
-                                 d, H, segtab2, Tc2, ops2, dabar, dep2, st));
-    ffk::AccumGeometry geo = ffk::accumulate_geometry(W_block, A, G, d, G);
-    FFK_HIP(ffk::launch_accumulate(omega_block, W_block, segtab, ops, G, d, A, geo, Y, st));
-    FFK_HIP(ffk::launch_segment_prefix_sum(Y, G, size_t(A)*dd*W_block, st));
-    FFK_HIP(ffk::launch_filter_function_derivative(omega_block, W_block, eigvals, dt, t, ops, dabar, Y,
-                                                   n_coeffs_ratio, G, d, A, H, dE,
+    FFK_HIP(ffk::launch_filter_function_derivative(omega_block, W_block, eigvals, dt, t, f.ops, f.abar, f.Y,
+                                                   n_coeffs_ratio, G, d, A, H, f.E,
                                                    filter_function_derivative, st));
     if (infidelity_derivative) {
         const int srows = s_ndim == 2 ? A : 1;

@@ -124,16 +124,6 @@ ResidentLayout resident_layout(int G, int d, int W, int N, int A) {
     return L;
 }
 
-// The spectrum of an infidelity integral as the kernels read it: `rows` rows of W c128 values (one for all selected
-// noise operators, one each, or one per pair), and the `n_out` integrals it gives per pulse.
-struct SpectrumShape {
-    size_t rows = 0, n_out = 0;
-};
-SpectrumShape spectrum_shape(int s_ndim, int n_idx) {
-    return {s_ndim == 1 ? 1 : (s_ndim == 2 ? size_t(n_idx) : size_t(n_idx)*n_idx),
-            s_ndim == 3 ? size_t(n_idx)*n_idx : size_t(n_idx)};
-}
-
 // `others_ok`: what else the entry point asks of its spectrum arguments (an output array, W >= 2)
 int check_spectrum_args(int s_ndim, const int32_t* idx, int n_idx, int A, int d, bool others_ok) {
     FFK_REQUIRE(idx && s_ndim >= 1 && s_ndim <= 3 && n_idx >= 1 && n_idx <= A && d >= 1 && others_ok,

@@ -39,32 +39,21 @@ int ffk_control_matrix_from_atomic(const double* phases, const double* control_m
     FFK_REQUIRE(control_matrix_atomic && out, "NULL argument");
     FFK_REQUIRE(G == 1 || (phases && propagators_liouville), "NULL argument");
     FFK_REQUIRE(which == 0 || which == 1, "invalid which=%d", which);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nP = 16*size_t(G > 1 ? G - 1 : 1)*W, nR = 16*size_t(G)*A*N*W;
-    const size_t nL = (l_is_complex ? 16 : 8)*size_t(G > 1 ? G - 1 : 1)*N*N;
-    const size_t nO = which ? nR : 16*size_t(A)*N*W;
+    StagedCall c;
+    const size_t nl = G > 1 ? G - 1 : 1, l_doubles = l_is_complex ? 2 : 1;
     const size_t wsb = ffk_control_matrix_from_atomic_workspace_bytes(G, A, N, W);
-    void* base;
-    if (int rc = arena_reserve(align_up(nP) + align_up(nR) + align_up(nL) + align_up(nO) + wsb, &base))
-        return rc;
-    Bump a(base, g_arena.size);
-    double* dP = a.take<double>(nP/8);
-    double* dR = a.take<double>(nR/8);
-    double* dL = a.take<double>(nL/8);
-    double* dO = a.take<double>(nO/8);
-    void* ws = a.take<unsigned char>(wsb);
-    if (G > 1) {
-        FFK_HIP(hipMemcpyAsync(dP, phases, 16*size_t(G - 1)*W, hipMemcpyHostToDevice, nullptr));
-        FFK_HIP(hipMemcpyAsync(dL, propagators_liouville, (l_is_complex ? 16 : 8)*size_t(G - 1)*N*N,
-                               hipMemcpyHostToDevice, nullptr));
-    }
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix_atomic, nR, hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_control_matrix_from_atomic_dev(dP, dR, dL, l_is_complex, G, A, N, W, which, dO, ws,
+    // G = 1: no phases and no propagators to copy, the kernel reads neither
+    const auto P = c.in<double>(phases, 2*nl*W, 2*size_t(G - 1)*W);
+    const auto R = c.in<double>(control_matrix_atomic, 2*size_t(G)*A*N*W);
+    const auto L = c.in<double>(propagators_liouville, l_doubles*nl*N*N, l_doubles*size_t(G - 1)*N*N);
+    const auto O = c.out<double>(2*size_t(which ? G : 1)*A*N*W);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_control_matrix_from_atomic_dev(c[P], c[R], c[L], l_is_complex, G, A, N, W, which, c[O], c[ws],
                                                     wsb, nullptr))
         return rc;
-    FFK_HIP(hipMemcpyAsync(out, dO, nO, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    if (int rc = c.copy_back(out, O)) return rc;
+    return c.finish();
 }
 
 int ffk_control_matrix_from_atomic_indexed_dev(const double* total_phases,
@@ -100,34 +89,21 @@ int ffk_control_matrix_from_atomic_indexed(const double* total_phases,
     FFK_REQUIRE(which == 0 || which == 1, "invalid which=%d", which);
     for (int g = 0; g < G; ++g)
         FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%d] = %d outside [0, %d)", g, index[g], T);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nP = 16*size_t(T)*W, nR = 16*size_t(T)*A*N*W, nI = 4*size_t(G);
-    const size_t nL = (l_is_complex ? 16 : 8)*size_t(G > 1 ? G - 1 : 1)*N*N;
-    const size_t nO = which ? 16*size_t(G)*A*N*W : 16*size_t(A)*N*W;
+    StagedCall c;
+    const size_t nl = G > 1 ? G - 1 : 1, l_doubles = l_is_complex ? 2 : 1;
     const size_t wsb = ffk_control_matrix_from_atomic_workspace_bytes(G, A, N, W);
-    void* base;
-    if (int rc = arena_reserve(align_up(nP) + align_up(nR) + align_up(nI) + align_up(nL) + align_up(nO) + wsb,
-                               &base))
+    const auto P = c.in<double>(total_phases, 2*size_t(T)*W);
+    const auto R = c.in<double>(control_matrix_table, 2*size_t(T)*A*N*W);
+    const auto I = c.in<int32_t>(index, G);
+    const auto L = c.in<double>(propagators_liouville, l_doubles*nl*N*N, l_doubles*size_t(G - 1)*N*N);
+    const auto O = c.out<double>(2*size_t(which ? G : 1)*A*N*W);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_control_matrix_from_atomic_indexed_dev(c[P], c[R], c[I], c[L], l_is_complex, T, G, A, N, W,
+                                                            which, c[O], c[ws], wsb, nullptr))
         return rc;
-    Bump a(base, g_arena.size);
-    double* dP = a.take<double>(nP/8);
-    double* dR = a.take<double>(nR/8);
-    int32_t* dI = a.take<int32_t>(G);
-    double* dL = a.take<double>(nL/8);
-    double* dO = a.take<double>(nO/8);
-    void* ws = a.take<unsigned char>(wsb);
-    FFK_HIP(hipMemcpyAsync(dP, total_phases, nP, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix_table, nR, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dI, index, nI, hipMemcpyHostToDevice, nullptr));
-    if (G > 1)
-        FFK_HIP(hipMemcpyAsync(dL, propagators_liouville, (l_is_complex ? 16 : 8)*size_t(G - 1)*N*N,
-                               hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_control_matrix_from_atomic_indexed_dev(dP, dR, dI, dL, l_is_complex, T, G, A, N, W,
-                                                            which, dO, ws, wsb, nullptr))
-        return rc;
-    FFK_HIP(hipMemcpyAsync(out, dO, nO, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    if (int rc = c.copy_back(out, O)) return rc;
+    return c.finish();
 }
 
 }  // extern "C"
@@ -266,32 +242,22 @@ int ffk_concatenate_sequence(const double* total_propagators, const double* tota
     FFK_REQUIRE(which == 0 || which == 1, "invalid which=%d", which);
     for (int g = 0; g < G; ++g)
         FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%d] = %d outside [0, %d)", g, index[g], T);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
+    StagedCall c;
     const size_t dd = size_t(d)*d;
-    const size_t nU = 16*size_t(T)*dd, nP = 16*size_t(T)*W, nR = 16*size_t(T)*A*N*W, nI = 4*size_t(G);
-    const size_t nB = 16*size_t(N)*dd;
-    void* base;
-    if (int rc = arena_reserve(align_up(nU) + align_up(nP) + align_up(nR) + align_up(nI) + align_up(nB) +
-                               sequence_scratch_bytes(G, d, A, N, W, which, hermitian_basis != 0,
-                                                      filter_function != nullptr), &base))
+    const auto U = c.in<double>(total_propagators, 2*size_t(T)*dd);
+    const auto P = c.in<double>(total_phases, 2*size_t(T)*W);
+    const auto R = c.in<double>(control_matrix_table, 2*size_t(T)*A*N*W);
+    const auto I = c.in<int32_t>(index, G);
+    const auto B = c.in<double>(basis, 2*size_t(N)*dd);
+    const auto scratch = c.workspace(sequence_scratch_bytes(G, d, A, N, W, which, hermitian_basis != 0,
+                                                            filter_function != nullptr));
+    if (int rc = c.stage()) return rc;
+    Bump a = c.bump(scratch);
+    if (int rc = sequence_on_device(c[U], c[P], c[R], c[I], c[B], hermitian_basis, T, G, d, A, N, W, which, a,
+                                    control_matrix, total_propagator, propagators_liouville, filter_function,
+                                    nullptr))
         return rc;
-    Bump a(base, g_arena.size);
-    double* dU = a.take<double>(nU/8);
-    double* dP = a.take<double>(nP/8);
-    double* dR = a.take<double>(nR/8);
-    int32_t* dI = a.take<int32_t>(G);
-    double* dB = a.take<double>(nB/8);
-    FFK_HIP(hipMemcpyAsync(dU, total_propagators, nU, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dI, index, nI, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dB, basis, nB, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dP, total_phases, nP, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix_table, nR, hipMemcpyHostToDevice, nullptr));
-    if (int rc = sequence_on_device(dU, dP, dR, dI, dB, hermitian_basis, T, G, d, A, N, W, which, a,
-                                    control_matrix, total_propagator, propagators_liouville,
-                                    filter_function, nullptr))
-        return rc;
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    return c.finish();
 }
 
 size_t ffk_control_matrix_periodic_workspace_bytes(int A, int N, int W) {
@@ -321,25 +287,19 @@ int ffk_control_matrix_periodic(const double* phases, const double* control_matr
     FFK_REQUIRE(A >= 1 && N >= 1 && W >= 1, "empty axis: A=%d N=%d W=%d", A, N, W);
     FFK_REQUIRE(repeats >= 1, "repeats = %d: need at least one period", repeats);
     FFK_REQUIRE(phases && control_matrix && total_propagator_liouville && out, "NULL argument");
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nP = 16*size_t(W), nR = 16*size_t(A)*N*W, nL = (l_is_complex ? 16 : 8)*size_t(N)*N;
+    StagedCall c;
     const size_t wsb = ffk_control_matrix_periodic_workspace_bytes(A, N, W);
-    void* base;
-    if (int rc = arena_reserve(align_up(nP) + 2*align_up(nR) + align_up(nL) + wsb, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dP = a.take<double>(nP/8);
-    double* dR = a.take<double>(nR/8);
-    double* dL = a.take<double>(nL/8);
-    double* dO = a.take<double>(nR/8);
-    void* ws = a.take<unsigned char>(wsb);
-    FFK_HIP(hipMemcpyAsync(dP, phases, nP, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix, nR, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dL, total_propagator_liouville, nL, hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_control_matrix_periodic_dev(dP, dR, dL, l_is_complex, repeats, A, N, W, dO, ws, wsb, nullptr))
+    const auto P = c.in<double>(phases, 2*size_t(W));
+    const auto R = c.in<double>(control_matrix, 2*size_t(A)*N*W);
+    const auto L = c.in<double>(total_propagator_liouville, (l_is_complex ? 2 : 1)*size_t(N)*N);
+    const auto O = c.out<double>(2*size_t(A)*N*W);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_control_matrix_periodic_dev(c[P], c[R], c[L], l_is_complex, repeats, A, N, W, c[O], c[ws], wsb,
+                                                 nullptr))
         return rc;
-    FFK_HIP(hipMemcpyAsync(out, dO, nR, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    if (int rc = c.copy_back(out, O)) return rc;
+    return c.finish();
 }
 
 int ffk_noise_operators_from_atomic(const double* phases, const double* noise_operators_atomic,
@@ -349,27 +309,17 @@ int ffk_noise_operators_from_atomic(const double* phases, const double* noise_op
     FFK_REQUIRE(G == 1 || (phases && propagators), "NULL argument");
     FFK_REQUIRE(G >= 1 && W >= 1 && A >= 1, "empty axis: G=%d W=%d A=%d", G, W, A);
     FFK_REQUIRE(d_templated_ok(d), "unsupported dimension d=%d (need 2 <= d <= %d)", d, FFK_MAX_D_TEMPLATED);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t dd = size_t(d)*d;
-    const size_t nph = 16*size_t(G > 1 ? G - 1 : 1)*W, nat = 16*size_t(G)*W*A*dd;
-    const size_t npr = 16*size_t(G > 1 ? G - 1 : 1)*dd, nout = 16*size_t(W)*A*dd;
-    void* base;
-    if (int rc = arena_reserve(align_up(nph) + align_up(nat) + align_up(npr) + align_up(nout), &base))
-        return rc;
-    Bump a(base, g_arena.size);
-    cplx* dph = a.take<cplx>(nph/16);
-    cplx* dat = a.take<cplx>(nat/16);
-    cplx* dpr = a.take<cplx>(npr/16);
-    cplx* dout = a.take<cplx>(nout/16);
-    if (G > 1) {
-        FFK_HIP(hipMemcpyAsync(dph, phases, 16*size_t(G - 1)*W, hipMemcpyHostToDevice, nullptr));
-        FFK_HIP(hipMemcpyAsync(dpr, propagators, 16*size_t(G - 1)*dd, hipMemcpyHostToDevice, nullptr));
-    }
-    FFK_HIP(hipMemcpyAsync(dat, noise_operators_atomic, nat, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(ffk::launch_noise_ops_from_atomic(dph, dat, dpr, G, W, A, d, dout, nullptr));
-    FFK_HIP(hipMemcpyAsync(noise_operators, dout, nout, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    StagedCall c;
+    const size_t dd = size_t(d)*d, nl = G > 1 ? G - 1 : 1;
+    // G = 1: no phases and no propagators to copy, the kernel reads neither
+    const auto ph = c.in<cplx>(phases, nl*W, size_t(G - 1)*W);
+    const auto at = c.in<cplx>(noise_operators_atomic, size_t(G)*W*A*dd);
+    const auto pr = c.in<cplx>(propagators, nl*dd, size_t(G - 1)*dd);
+    const auto out = c.out<cplx>(size_t(W)*A*dd);
+    if (int rc = c.stage()) return rc;
+    FFK_HIP(ffk::launch_noise_ops_from_atomic(c[ph], c[at], c[pr], G, W, A, d, c[out], nullptr));
+    if (int rc = c.copy_back(noise_operators, out)) return rc;
+    return c.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -417,32 +367,21 @@ int ffk_decay_amplitudes(const double* control_matrix, int n_pulses, int A, int 
     FFK_REQUIRE(n_pulses >= 1 && A >= 1 && N >= 1 && W >= 1 && n_idx >= 1, "empty axis");
     for (int i = 0; i < n_idx; ++i)
         FFK_REQUIRE(idx[i] >= 0 && idx[i] < A, "noise operator index %d out of range [0, %d)", idx[i], A);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nR = 16*size_t(n_pulses)*A*N*W;
-    const size_t nS = 16*size_t(W)*(s_ndim == 1 ? 1 : (s_ndim == 2 ? n_idx : size_t(n_idx)*n_idx));
-    const size_t nout = size_t(n_pulses)*n_pulses*n_idx*(s_ndim == 3 ? n_idx : 1)*N*N;
+    StagedCall c;
+    const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
     const size_t wsb = ffk_decay_amplitudes_workspace_bytes(n_pulses, N, W, n_idx, s_ndim);
-    void* base;
-    if (int rc = arena_reserve(align_up(nR) + align_up(nS) + align_up(8*size_t(W)) +
-                                   align_up(4*size_t(n_idx)) + align_up(8*nout) + wsb, &base))
+    const auto R = c.in<double>(control_matrix, 2*size_t(n_pulses)*A*N*W);
+    const auto S = c.in<double>(spectrum, 2*size_t(W)*sh.rows);
+    const auto om = c.in<double>(omega, W);
+    const auto didx = c.in<int32_t>(idx, n_idx);
+    const auto out = c.out<double>(size_t(n_pulses)*n_pulses*sh.n_out*N*N);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_decay_amplitudes_dev(c[R], n_pulses, A, N, W, c[S], s_ndim, c[om], c[didx], n_idx, c[out],
+                                          c[ws], wsb, nullptr))
         return rc;
-    Bump a(base, g_arena.size);
-    double* dR = a.take<double>(nR/8);
-    double* dS = a.take<double>(nS/8);
-    double* dom = a.take<double>(W);
-    int32_t* didx = a.take<int32_t>(n_idx);
-    double* dout = a.take<double>(nout);
-    void* ws = a.take<unsigned char>(wsb);
-    FFK_HIP(hipMemcpyAsync(dR, control_matrix, nR, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dS, spectrum, nS, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dom, omega, 8*size_t(W), hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(didx, idx, 4*size_t(n_idx), hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_decay_amplitudes_dev(dR, n_pulses, A, N, W, dS, s_ndim, dom, didx, n_idx, dout,
-                                          ws, wsb, nullptr))
-        return rc;
-    FFK_HIP(hipMemcpyAsync(decay_amplitudes, dout, 8*nout, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    if (int rc = c.copy_back(decay_amplitudes, out)) return rc;
+    return c.finish();
 }
 
 size_t ffk_cumulant_function_workspace_bytes(int batch, int N, int d) {
@@ -474,24 +413,17 @@ int ffk_cumulant_function(const double* decay_amplitudes, int batch, int N, int 
     FFK_REQUIRE(decay_amplitudes && basis && cumulant_function, "NULL argument");
     FFK_REQUIRE(batch >= 1 && N >= 1, "empty axis");
     FFK_REQUIRE(d_ok(d), "dimension %d outside [2, %d]", d, FFK_MAX_D);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nG = 8*size_t(batch)*N*N;
-    const size_t nB = 16*size_t(N)*d*d;
+    StagedCall c;
     const size_t wsb = single_qubit ? 0 : ffk_cumulant_function_workspace_bytes(batch, N, d);
-    void* base;
-    if (int rc = arena_reserve(2*align_up(nG) + align_up(nB) + wsb + 256, &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dG = a.take<double>(nG/8);
-    double* dK = a.take<double>(nG/8);
-    double* dB = a.take<double>(nB/8);
-    void* ws = a.take<unsigned char>(wsb + 16);
-    FFK_HIP(hipMemcpyAsync(dG, decay_amplitudes, nG, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(hipMemcpyAsync(dB, basis, nB, hipMemcpyHostToDevice, nullptr));
-    if (int rc = ffk_cumulant_function_dev(dG, batch, N, d, dB, single_qubit, dK, ws, wsb, nullptr))
+    const auto dG = c.in<double>(decay_amplitudes, size_t(batch)*N*N);
+    const auto K = c.out<double>(size_t(batch)*N*N);
+    const auto B = c.in<double>(basis, 2*size_t(N)*d*d);
+    const auto ws = c.workspace(wsb);
+    if (int rc = c.stage()) return rc;
+    if (int rc = ffk_cumulant_function_dev(c[dG], batch, N, d, c[B], single_qubit, c[K], c[ws], wsb, nullptr))
         return rc;
-    FFK_HIP(hipMemcpyAsync(cumulant_function, dK, nG, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    if (int rc = c.copy_back(cumulant_function, K)) return rc;
+    return c.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -515,20 +447,17 @@ int ffk_expm_real(const double* matrix, int N, double* result) {
         norm = col > norm ? col : norm;
     }
     const int squarings = squarings_for(norm);
-    std::lock_guard<std::mutex> lock(g_arena.mu);
-    const size_t nb = 8*size_t(N)*N;
-    void* base;
-    if (int rc = arena_reserve(7*align_up(nb), &base)) return rc;
-    Bump a(base, g_arena.size);
-    double* dA = a.take<double>(nb/8);
-    double* dO = a.take<double>(nb/8);
+    StagedCall c;
+    const auto dA = c.in<double>(matrix, size_t(N)*N);
+    const auto dO = c.out<double>(size_t(N)*N);
+    StagedCall::Slice<double> sw[5];
+    for (auto& m : sw) m = c.out<double>(size_t(N)*N);
+    if (int rc = c.stage()) return rc;
     double* w[5];
-    for (double*& m : w) m = a.take<double>(nb/8);
-    FFK_HIP(hipMemcpyAsync(dA, matrix, nb, hipMemcpyHostToDevice, nullptr));
-    FFK_HIP(ffk::launch_expm_real(dA, N, squarings, dO, w, nullptr));
-    FFK_HIP(hipMemcpyAsync(result, dO, nb, hipMemcpyDeviceToHost, nullptr));
-    FFK_HIP(hipStreamSynchronize(nullptr));
-    return FFK_OK;
+    for (int i = 0; i < 5; ++i) w[i] = c[sw[i]];
+    FFK_HIP(ffk::launch_expm_real(c[dA], N, squarings, c[dO], w, nullptr));
+    if (int rc = c.copy_back(result, dO)) return rc;
+    return c.finish();
 }
 
 size_t ffk_error_transfer_matrix_workspace_bytes(int N) {

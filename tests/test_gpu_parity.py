@@ -3317,3 +3317,364 @@ def test_cumulant_function_and_error_transfer_matrix_above_d16(d, btype):
         numeric.calculate_control_matrix_from_scratch(pulse.eigvals, pulse.eigvecs, pulse.propagators, omega, basis,
                                                       pulse.n_opers, pulse.n_coeffs, pulse.dt,
                                                       cache_intermediates=True)
+
+
+# ---------------------------------------------------------------------------------------------
+# Host-pointer entry points: every one stages its arrays through the process-wide arena
+# ---------------------------------------------------------------------------------------------
+def _hostcall_cases(d, G, A, H, W, n_idx=2, T=3, seed=11, basis=None):
+    """name -> thunk that runs one host-pointer entry point of libffk on fixed random inputs and returns its outputs.
+    The inputs only have the right shapes and dtypes (no kernel's control flow depends on values), which is all that
+    staging can get wrong; `slow` marks the entry points of ffk_api_frozen.hip."""
+    lib = _lib.load()
+    rng = np.random.default_rng(seed)
+    p = _lib.ptr
+    N = d*d
+    basis = np.ascontiguousarray(ff.Basis.ggm(d) if basis is None else basis, dtype=complex)
+
+    def c128(*shape):
+        return rng.standard_normal(shape) + 1j*rng.standard_normal(shape)
+
+    def herm(n):
+        M = c128(n, d, d)
+        return np.ascontiguousarray(M + M.conj().transpose(0, 2, 1))
+
+    def run(fn, outputs, *args):
+        _lib.check(fn(*args))
+        return outputs
+
+    Hm, n_opers, c_opers = herm(G), herm(A), herm(H)
+    dt = rng.random(G) + 0.2
+    t = np.concatenate(([0.0], np.cumsum(dt)))
+    D = np.ascontiguousarray(rng.standard_normal((G, d)))
+    V, Q = c128(G, d, d)/d, c128(G + 1, d, d)/d
+    omega = np.sort(rng.random(W))*20 + 1e-2
+    n_coeffs, ratio = rng.random((A, G)) + 0.1, rng.random((A, H, G))
+    idx = np.arange(n_idx, dtype=np.int32)[::-1].copy()
+    spectra = {1: c128(W), 2: c128(n_idx, W), 3: c128(n_idx, n_idx, W)}
+    n_out = {1: n_idx, 2: n_idx, 3: n_idx*n_idx}
+    R, F, F2 = c128(A, N, W), c128(A, A, W), c128(A, A, N, N, W)
+    index = rng.integers(0, T, G).astype(np.int32)
+    phases, table, U = c128(T, W), c128(T, A, N, W), c128(T, d, d)/d
+    L = np.ascontiguousarray(rng.standard_normal((max(G - 1, 1), N, N))/N)
+    pulse_args = (p(D), p(V), p(Q), p(omega), W, p(basis), N, p(n_opers), A, p(n_coeffs), p(dt), p(t), G, d)
+    no_basis = pulse_args[:5] + pulse_args[7:]
+    grad_args = (*no_basis[:8], p(c_opers), H)
+    cases, slow = {}, set()
+
+    def diagonalize():
+        o = np.empty((G, d)), np.empty((G, d, d), complex), np.empty((G + 1, d, d), complex)
+        return run(lib.ffk_diagonalize, o, p(Hm), p(dt), G, d, *map(p, o))
+    cases['diagonalize'] = diagonalize
+
+    def control_matrix(flags):
+        o = np.empty((A, N, W), complex), (np.empty((W, A, d, d), complex) if flags else None)
+        return run(lib.ffk_control_matrix, o, *pulse_args, flags, *map(p, o))
+    cases['control_matrix'] = lambda: control_matrix(0)
+    cases['control_matrix+noise_operators'] = lambda: control_matrix(_lib.WANT_NOISE_OPERATORS)
+
+    def intermediates():
+        o = [np.empty(s, complex) for s in ((A, G, d, d), (G, d, d), (G, N, d, d), (G, W), (G, W, d, d), (G, A, N, W))]
+        return run(lib.ffk_control_matrix_intermediates, o, *pulse_args, *map(p, o))
+    cases['control_matrix_intermediates'] = intermediates
+
+    def noise_intermediates():
+        o = [np.empty(s, complex) for s in ((A, G, d, d), (G, W), (G, W, d, d), (G, W, A, d, d))]
+        return run(lib.ffk_noise_operators_intermediates, o, *no_basis, *map(p, o))
+    cases['noise_operators_intermediates'] = noise_intermediates
+
+    def filter_function(which):
+        o = [np.empty((A, A, N, N, W) if which else (A, A, W), complex)]
+        return run(lib.ffk_filter_function, o, p(R), A, N, W, which, p(o[0]))
+    weights = c128(N, N)
+
+    def filter_function_weighted():
+        o = [np.empty((A, A, W), complex)]
+        return run(lib.ffk_filter_function_weighted, o, p(R), A, N, W, p(weights), 0.5, p(o[0]))
+    cases['filter_function_weighted'] = filter_function_weighted
+
+    def infidelity(nd):
+        o = [np.empty(n_out[nd])]
+        return run(lib.ffk_infidelity, o, p(F), A, W, p(spectra[nd]), nd, p(omega), p(idx), n_idx, d, p(o[0]))
+
+    def liouville():
+        o = [np.empty((T, N, N))]
+        return run(lib.ffk_liouville, o, p(U), T, d, p(basis), N, 1, p(o[0]))
+    cases['liouville'] = liouville
+
+    step_phases, atomic = c128(max(G - 1, 1), W), c128(G, A, N, W)
+
+    def from_atomic(which, g):
+        o = [np.empty((g, A, N, W) if which else (A, N, W), complex)]
+        return run(lib.ffk_control_matrix_from_atomic, o, p(step_phases) if g > 1 else None, p(atomic),
+                   p(L) if g > 1 else None, 0, g, A, N, W, which, p(o[0]))
+
+    def from_atomic_indexed(which):
+        o = [np.empty((G, A, N, W) if which else (A, N, W), complex)]
+        return run(lib.ffk_control_matrix_from_atomic_indexed, o, p(phases), p(table), p(index), p(L), 0, T, G, A, N,
+                   W, which, p(o[0]))
+
+    def concatenate_sequence(which):
+        o = [np.empty((G, A, N, W) if which else (A, N, W), complex), np.empty((d, d), complex),
+             np.empty((max(G - 1, 1), N, N)), None if which else np.empty((A, A, W), complex)]
+        return run(lib.ffk_concatenate_sequence, o, p(U), p(phases), p(table), p(index), p(basis), 1, T, G, d, A, N, W,
+                   which, *map(p, o))
+
+    def periodic():
+        o = [np.empty((A, N, W), complex)]
+        return run(lib.ffk_control_matrix_periodic, o, p(phases), p(R), p(L), 0, 5, A, N, W, p(o[0]))
+    cases['control_matrix_periodic'] = periodic
+    B_atomic, props = c128(G, W, A, d, d), c128(max(G - 1, 1), d, d)/d
+
+    def noise_operators_from_atomic(g):
+        o = [np.empty((W, A, d, d), complex)]
+        return run(lib.ffk_noise_operators_from_atomic, o, p(step_phases) if g > 1 else None, p(B_atomic),
+                   p(props) if g > 1 else None, g, W, A, d, p(o[0]))
+    for g in (G, 1):
+        cases[f'control_matrix_from_atomic G={g}'] = lambda g=g: from_atomic(0, g)
+        cases[f'noise_operators_from_atomic G={g}'] = lambda g=g: noise_operators_from_atomic(g)
+
+    def decay_amplitudes(nd):
+        o = [np.empty((T, T, n_out[nd], N, N))]
+        return run(lib.ffk_decay_amplitudes, o, p(table), T, A, N, W, p(spectra[nd]), nd, p(omega), p(idx), n_idx,
+                   p(o[0]))
+    gamma = np.ascontiguousarray(rng.standard_normal((T, N, N)))
+
+    def cumulant_function():
+        o = [np.empty((T, N, N))]
+        return run(lib.ffk_cumulant_function, o, p(gamma), T, N, d, p(basis), 0, p(o[0]))
+    cases['cumulant_function'] = cumulant_function
+    pauli, gamma_1q = np.ascontiguousarray(ff.Basis.pauli(1), dtype=complex), rng.standard_normal((T, 4, 4))
+
+    def cumulant_function_single_qubit():        # a workspace of zero bytes
+        o = [np.empty((T, 4, 4))]
+        return run(lib.ffk_cumulant_function, o, p(gamma_1q), T, 4, 2, p(pauli), 1, p(o[0]))
+    cases['cumulant_function single qubit'] = cumulant_function_single_qubit
+
+    def expm_real():
+        o = [np.empty((N, N))]
+        return run(lib.ffk_expm_real, o, p(gamma), N, p(o[0]))
+    cases['expm_real'] = expm_real
+
+    # ---- ffk_api_frozen.hip
+    def second_order():
+        o = [np.empty((A, A, N, N, W), complex)]
+        return run(lib.ffk_second_order_filter_function, o, *pulse_args, p(o[0]))
+
+    def shifts_from_scratch(nd):
+        o = [np.empty((A, A, N, N, W), complex), np.empty((n_out[nd], N, N))]
+        return run(lib.ffk_frequency_shifts_from_scratch, o, *pulse_args, p(spectra[nd]), nd, p(idx), n_idx,
+                   *map(p, o))
+    F_atomic, R_step = c128(G, A, A, N, N, W), c128(G, A, N, W)
+
+    def second_order_from_atomic():
+        o = [np.empty((A, A, N, N, W), complex)]
+        return run(lib.ffk_second_order_filter_function_from_atomic, o, p(F_atomic), p(R_step), p(L), G, A, N, W,
+                   p(o[0]))
+
+    def frequency_shifts(nd):
+        o = [np.empty((n_out[nd], N, N))]
+        return run(lib.ffk_frequency_shifts, o, p(F2), A, N, W, p(spectra[nd]), nd, p(omega), p(idx), n_idx, p(o[0]))
+
+    def cumulant_second_order():                  # adds to the array it is given
+        o = [gamma + 1.0]
+        return run(lib.ffk_cumulant_function_second_order, o, p(gamma), T, N, d, p(basis), p(o[0]))
+    grad_spectra = {1: c128(W), 2: c128(A, W)}
+
+    def derivative(nd, with_ratio, want_dF=True):
+        o = [np.empty((A, G, H, W)) if want_dF else None, np.empty((A, G, H)) if nd else None]
+        return run(lib.ffk_filter_function_derivative, o, *grad_args, p(ratio) if with_ratio else None, p(dt), p(t), G,
+                   d, p(grad_spectra[nd]) if nd else None, nd, *map(p, o))
+
+    def control_matrix_derivative():
+        o = [np.empty((H, W, G, A, N), complex)]
+        return run(lib.ffk_control_matrix_derivative, o, *pulse_args[:10], p(c_opers), H, p(ratio), p(dt), p(t), G, d,
+                   p(o[0]))
+    dR = c128(H, W, G, A, N)
+
+    def derivative_from_control_matrix():
+        o = [np.empty((A, G, H, W))]
+        return run(lib.ffk_filter_function_derivative_from_control_matrix, o, p(R), p(dR), A, N, W, G, H, p(o[0]))
+
+    for which in (0, 1):
+        cases[f'filter_function which={which}'] = lambda w=which: filter_function(w)
+        cases[f'control_matrix_from_atomic which={which}'] = lambda w=which: from_atomic(w, G)
+        cases[f'control_matrix_from_atomic_indexed which={which}'] = lambda w=which: from_atomic_indexed(w)
+        cases[f'concatenate_sequence which={which}'] = lambda w=which: concatenate_sequence(w)
+    for nd in (1, 2, 3):
+        cases[f'infidelity s_ndim={nd}'] = lambda nd=nd: infidelity(nd)
+        cases[f'decay_amplitudes s_ndim={nd}'] = lambda nd=nd: decay_amplitudes(nd)
+        cases[f'frequency_shifts_from_scratch s_ndim={nd}'] = lambda nd=nd: shifts_from_scratch(nd)
+        cases[f'frequency_shifts s_ndim={nd}'] = lambda nd=nd: frequency_shifts(nd)
+    cases.update({
+        'second_order_filter_function': second_order, 'second_order_filter_function_from_atomic': second_order_from_atomic,
+        'cumulant_function_second_order': cumulant_second_order,
+        'filter_function_derivative': lambda: derivative(0, True),
+        'infidelity_derivative s_ndim=1': lambda: derivative(1, False),
+        'infidelity_derivative s_ndim=2': lambda: derivative(2, True),
+        'infidelity_derivative alone': lambda: derivative(2, True, want_dF=False),
+        'control_matrix_derivative': control_matrix_derivative,
+        'filter_function_derivative_from_control_matrix': derivative_from_control_matrix})
+    frozen = ('frequency_shifts', 'second_order', 'cumulant_function_second_order', 'derivative')
+    slow = {name for name in cases if any(key in name for key in frozen)}
+    if d > 8:
+        cases = {k: v for k, v in cases.items() if 'derivative' not in k}       # the gradient kernels: d <= 8
+    inputs = dict(D=D, V=V, Q=Q, omega=omega, n_opers=n_opers, n_coeffs=n_coeffs, c_opers=c_opers, ratio=ratio, dt=dt,
+                  t=t, basis=basis, idx=idx, spectra=spectra, grad_spectra=grad_spectra)
+    return cases, slow, inputs
+
+
+def _same_bits(got, ref):
+    return all((a is None and b is None) or a.tobytes() == b.tobytes() for a, b in zip(got, ref))
+
+
+_HOSTCALL_SHAPE = dict(d=3, G=4, A=2, H=2, W=33)       # N = 9 (GGM), W no multiple of a wavefront
+_hostcall_memo = {}
+
+
+def _hostcall_reference():
+    """The cases at _HOSTCALL_SHAPE and, computed once, the result of each directly after ffk_release_arena()."""
+    if not _hostcall_memo:
+        cases, slow, inputs = _hostcall_cases(**_HOSTCALL_SHAPE)
+        _hostcall_memo.update(cases=cases, slow=slow, inputs=inputs, fresh={})
+    return _hostcall_memo
+
+
+def _fresh_result(name):
+    memo = _hostcall_reference()
+    if name not in memo['fresh']:
+        _lib.check(_lib.load().ffk_release_arena())
+        memo['fresh'][name] = [None if o is None else o.copy() for o in memo['cases'][name]()]
+    return memo['fresh'][name]
+
+
+def _grow_arena():
+    """A call that leaves the arena far larger than any case at _HOSTCALL_SHAPE needs (7 x 2 MiB)."""
+    M = np.zeros((512, 512))
+    _lib.check(_lib.load().ffk_expm_real(_lib.ptr(M), 512, _lib.ptr(np.empty_like(M))))
+
+
+def _check_arena_history(names):
+    memo = _hostcall_reference()
+    assert names
+    for name in names:
+        fresh = _fresh_result(name)
+        _grow_arena()
+        grown = memo['cases'][name]()
+        assert all(o is None or np.isfinite(o).all() for o in fresh), name
+        assert _same_bits(grown, fresh), f'{name}: the result depends on what the arena held before'
+
+
+def test_host_pointer_results_do_not_depend_on_the_arenas_history():
+    """Each host-pointer entry point of ffk_api.hip and ffk_api_sequence.hip, once on a freshly released arena (the
+    reservation is then barely larger than the call's own need, so arrays whose sizes were under-counted overlap)
+    and once on an arena that a larger call has grown: bit-identical outputs."""
+    memo = _hostcall_reference()
+    _check_arena_history([n for n in memo['cases'] if n not in memo['slow']])
+
+
+@pytest.mark.slow
+def test_frozen_host_pointer_results_do_not_depend_on_the_arenas_history():
+    """... and those of ffk_api_frozen.hip: second order, frequency shifts, gradients."""
+    memo = _hostcall_reference()
+    _check_arena_history(sorted(memo['slow']))
+
+
+def _dev_buffers(*arrays):
+    import torch
+    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
+def _dptr(tensor):
+    return None if tensor is None else tensor.data_ptr()
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize('s_ndim', [1, 2, 3])
+def test_host_second_order_call_equals_its_device_pointer_twin(s_ndim):
+    """ffk_frequency_shifts_from_scratch against ffk_second_order_filter_function_dev followed by
+    ffk_frequency_shifts_shard_dev on the whole grid, each with a workspace of exactly the queried size."""
+    import torch
+    lib, memo = _lib.load(), _hostcall_reference()
+    i, sh = memo['inputs'], _HOSTCALL_SHAPE
+    d, G, A, W = sh['d'], sh['G'], sh['A'], sh['W']
+    N, n_idx = d*d, len(i['idx'])
+    n_out = n_idx*n_idx if s_ndim == 3 else n_idx
+    host = _fresh_result(f'frequency_shifts_from_scratch s_ndim={s_ndim}')
+    D, V, Q, om, basis, nop, nc, dt, t, S, idx = _dev_buffers(
+        i['D'], i['V'], i['Q'], i['omega'], i['basis'], i['n_opers'], i['n_coeffs'], i['dt'], i['t'],
+        i['spectra'][s_ndim], i['idx'])
+    F2 = torch.empty((A, A, N, N, W), dtype=torch.complex128, device='cuda')
+    shifts = torch.empty((n_out, N, N), dtype=torch.float64, device='cuda')
+    wsb = lib.ffk_second_order_workspace_bytes(W, N, A, G, d)
+    swsb = lib.ffk_frequency_shifts_workspace_bytes(W, n_idx, s_ndim)
+    assert wsb > 0 and swsb > 0
+    ws, sws = (torch.empty(n, dtype=torch.uint8, device='cuda') for n in (wsb, swsb))
+    _lib.check(lib.ffk_second_order_filter_function_dev(
+        *map(_dptr, (D, V, Q, om)), W, _dptr(basis), N, _dptr(nop), A, *map(_dptr, (nc, dt, t)), G, d, _dptr(F2),
+        _dptr(ws), wsb, None))
+    _lib.check(lib.ffk_frequency_shifts_shard_dev(_dptr(F2), A, N, W, _dptr(S), s_ndim, _dptr(om), W, 0, _dptr(idx),
+                                                  n_idx, _dptr(shifts), _dptr(sws), swsb, None))
+    torch.cuda.synchronize()
+    assert _same_bits([F2.cpu().numpy(), shifts.cpu().numpy()], host)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize('s_ndim', [1, 2])
+def test_host_gradient_call_equals_its_device_pointer_twin(s_ndim):
+    """ffk_filter_function_derivative (filter function and infidelity derivative) against
+    ffk_filter_function_derivative_shard_dev on the whole grid with a workspace of exactly the queried size."""
+    import torch
+    lib, memo = _lib.load(), _hostcall_reference()
+    i, sh = memo['inputs'], _HOSTCALL_SHAPE
+    d, G, A, H, W = sh['d'], sh['G'], sh['A'], sh['H'], sh['W']
+    with_ratio = s_ndim == 2
+    host = _fresh_result(f'infidelity_derivative s_ndim={s_ndim}')
+    D, V, Q, om, nop, nc, cop, ratio, dt, t, S = _dev_buffers(
+        i['D'], i['V'], i['Q'], i['omega'], i['n_opers'], i['n_coeffs'], i['c_opers'],
+        i['ratio'] if with_ratio else None, i['dt'], i['t'], i['grad_spectra'][s_ndim])
+    dF = torch.empty((A, G, H, W), dtype=torch.float64, device='cuda')
+    dI = torch.empty((A, G, H), dtype=torch.float64, device='cuda')
+    wsb = lib.ffk_filter_function_derivative_workspace_bytes(W, A, H, G, d)
+    assert wsb > 0
+    ws = torch.empty(wsb, dtype=torch.uint8, device='cuda')
+    _lib.check(lib.ffk_filter_function_derivative_shard_dev(
+        *map(_dptr, (D, V, Q, om)), W, _dptr(nop), A, _dptr(nc), _dptr(cop), H, _dptr(ratio), _dptr(dt), _dptr(t), G,
+        d, _dptr(S), s_ndim, _dptr(om), W, 0, _dptr(dF), _dptr(dI), _dptr(ws), wsb, None))
+    torch.cuda.synchronize()
+    _lib.check_kernel_fault()
+    assert _same_bits([dF.cpu().numpy(), dI.cpu().numpy()], host)
+
+
+def test_host_pointer_calls_work_after_a_rejected_call():
+    """A host-pointer call that fails its argument check (FFK_EINVAL) leaves the arena usable: the same entry point
+    with good arguments then gives the result it gives on a fresh arena.  One entry point of ffk_api.hip, one of
+    ffk_api_sequence.hip."""
+    lib, memo = _lib.load(), _hostcall_reference()
+    sh = _HOSTCALL_SHAPE
+    A, N, W = sh['A'], sh['d']**2, sh['W']
+    R, out = np.ones((A, N, W), complex), np.empty((A, A, W), complex)
+    ref_F = _fresh_result('filter_function which=0')
+    ref_R = _fresh_result('control_matrix_periodic')
+    with pytest.raises(ValueError):
+        _lib.check(lib.ffk_filter_function(_lib.ptr(R), A, N, W, 7, _lib.ptr(out)))             # invalid `which`
+    assert _same_bits(memo['cases']['filter_function which=0'](), ref_F)
+    with pytest.raises(ValueError):
+        _lib.check(lib.ffk_control_matrix_periodic(_lib.ptr(R[0, 0]), _lib.ptr(R), _lib.ptr(np.eye(N)), 0, 0, A, N, W,
+                                                   _lib.ptr(np.empty_like(R))))                 # repeats < 1
+    assert _same_bits(memo['cases']['control_matrix_periodic'](), ref_R)
+
+
+@pytest.mark.slow
+def test_frozen_host_pointer_calls_work_after_a_rejected_call():
+    """... and one of ffk_api_frozen.hip: the gradient asked for an infidelity derivative without a spectrum."""
+    lib, memo = _lib.load(), _hostcall_reference()
+    ref = _fresh_result('infidelity_derivative s_ndim=2')
+    i, sh = memo['inputs'], _HOSTCALL_SHAPE
+    d, G, A, H, W = sh['d'], sh['G'], sh['A'], sh['H'], sh['W']
+    p = _lib.ptr
+    with pytest.raises(ValueError):
+        _lib.check(lib.ffk_filter_function_derivative(
+            p(i['D']), p(i['V']), p(i['Q']), p(i['omega']), W, p(i['n_opers']), A, p(i['n_coeffs']), p(i['c_opers']), H,
+            None, p(i['dt']), p(i['t']), G, d, None, 2, None, p(np.empty((A, G, H)))))
+    assert _same_bits(memo['cases']['infidelity_derivative s_ndim=2'](), ref)

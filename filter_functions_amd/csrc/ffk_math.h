@@ -276,4 +276,93 @@ FFK_HD cplx cexp(double x) {
     return out;
 }
 
+// ---------------------------------------------------------------------------------------
+// The nested integral of the gradient (gradient.py:69-108),
+//     J(x, b) = int_0^dt dtau e^{i x tau} int_0^tau dtau' e^{i b tau'},   x = omega + W_a,
+// from the first-order integrals I1(x) and I1(x + b) the gradient kernels hold anyway.  With
+// X = x dt, B = b dt and M_k = int_0^dt tau^k e^{i x tau} dtau (M_0 = I1(x)) three regimes:
+//   |B| >= theta          the reference's divided difference (I1(x + b) - I1(x))/(i b); its rounding
+//                         error is ~u/|B| of dt^2/2 (u = 2^-53), at most 4 u/theta = 4.5e-13;
+//   |B| <  theta (and 0)  J = sum_{k<4} (i b)^k/(k+1)! M_{k+1}   (the inner integral expanded in b;
+//                         the first term dropped is below theta^4/720 of dt^2), with
+//       |X| >= 2^-9       M_k = (dt^k e^{i x dt} - k M_{k-1})/(i x) upwards from I1.  Step k multiplies
+//                         the error by k/|X| and M_k enters with B^(k-1)/k!: M_1 costs 4 u/|X| <= 2.3e-13
+//                         of dt^2/2, M_2 256 u, M_3 128 u, M_4 64 u.  At b == 0 the sum is M_1, the
+//                         reference's own (dt e^{i x dt} - I1)/(i x);
+//       |X| <  2^-9       where that recurrence cancels (the reference loses u/|X| here, everything
+//                         at a resonance met to the last bit): M_4 from its Taylor series
+//                         sum_j (iX)^j/(j! (j+5)) (6 terms, remainder < 1e-20), then DOWNWARDS
+//                         k M_{k-1} = dt^k e^{i x dt} - i x M_k, which damps errors.
+// The reference (and the oracle) test b == 0 and x == 0 exactly and lose u/|B|, u/|X| next to
+// those points: a segment with amplitudes of 1e-9 or a level crossing costs them 7+ digits.
+// Which side of theta: per segment and level pair, not per frequency -- derivative_integral_rcp
+// is evaluated once where 1/W_mn used to be, and its zero selects the series.
+// ---------------------------------------------------------------------------------------
+constexpr double kDerivativeIntegralBand = 0.0009765625;      // theta = 2^-10
+constexpr double kDerivativeIntegralTaylor = 0.001953125;     // 2^-9: |x dt| below which the moments come from series
+
+// a constant materialised where it is used (pinned_bits): hoisted out of the callers' unrolled loops these
+// would take scalar registers that the fused batched kernel does not have
+#define FFK_PINNED(c) pinned_bits<__builtin_bit_cast(unsigned long long, static_cast<double>(c))>()
+
+// one Horner step of the series, S_J = 1/(J+5) + (iX/(J+1)) S_{J+1}
+template <int J>
+FFK_HD void derivative_integral_series_step(double X, cplx& S) {
+    const double f = X*FFK_PINNED(1.0/(J + 1));
+    S = {fma(-f, S.im, FFK_PINNED(1.0/(J + 5))), f*S.re};
+    if constexpr (J > 0) derivative_integral_series_step<J - 1>(X, S);
+}
+
+// 1/b for the divided difference; 0 where |b dt| < theta: the series
+FFK_HD double derivative_integral_rcp(double b, double dt) {
+    return fabs(b*dt) < kDerivativeIntegralBand ? 0.0 : 1.0/b;
+}
+
+// m_1 + (iB/2) (m_2 + (iB/3) (m_3 + (iB/4) m_4)), times unit
+FFK_HD cplx derivative_integral_sum(double B, double unit, cplx m1, cplx m2, cplx m3, cplx m4) {
+    const double B4 = 0.25*B, B2 = 0.5*B;
+    const double B3 = FFK_PINNED(1.0/3.0)*B;
+    cplx h = {fma(-B4, m4.im, m3.re), fma(B4, m4.re, m3.im)};
+    h = {fma(-B3, h.im, m2.re), fma(B3, h.re, m2.im)};
+    h = {fma(-B2, h.im, m1.re), fma(B2, h.re, m1.im)};
+    return {unit*h.re, unit*h.im};
+}
+
+// J(x, b); rb = derivative_integral_rcp(b, dt), i1x = I1(x), i1xb = I1(x + b).  The two series branches stand side
+// by side, not nested, and each one's condition is ONE comparison of a value made for it: one saved execution
+// mask at a time (the fused batched kernel has no scalar register to spare; a third branch that stops after
+// M_1 at b == 0 spills there).
+FFK_HD cplx derivative_integral(double x, double b, double rb, double dt, cplx i1x, cplx i1xb) {
+    const cplx df = {i1xb.re - i1x.re, i1xb.im - i1x.im};
+    cplx j = {df.im*rb, -df.re*rb};                                    // df/(i b)
+    const double X = x*dt;
+    const double up = rb == 0.0 ? fabs(X) : -1.0, down = rb == 0.0 ? fabs(X) : 1.0;
+    if (up >= kDerivativeIntegralTaylor) {
+        const cplx ex = {1.0 - x*i1x.im, x*i1x.re};                    // e^{i x dt} = 1 + i x I1
+        const double rx = 1.0/x;
+        const cplx m1 = {(dt*ex.im - i1x.im)*rx, -(dt*ex.re - i1x.re)*rx};         // (dt e^{i x dt} - I1)/(i x)
+        double p = dt*dt;
+        const cplx m2 = {(p*ex.im - 2.0*m1.im)*rx, -(p*ex.re - 2.0*m1.re)*rx};
+        p *= dt;
+        const cplx m3 = {(p*ex.im - 3.0*m2.im)*rx, -(p*ex.re - 3.0*m2.re)*rx};
+        p *= dt;
+        const cplx m4 = {(p*ex.im - 4.0*m3.im)*rx, -(p*ex.re - 4.0*m3.re)*rx};
+        j = derivative_integral_sum(b, 1.0, m1, m2, m3, m4);
+    }
+    if (down < kDerivativeIntegralTaylor) {
+        // m_k = M_k/dt^(k+1) = int_0^1 u^k e^{i X u} du; Horner S_j = 1/(j+5) + (iX/(j+1)) S_{j+1}
+        const cplx ex = {1.0 - x*i1x.im, x*i1x.re};
+        cplx m4 = {FFK_PINNED(1.0/10.0), 0.0};                         // j = 5
+        derivative_integral_series_step<4>(X, m4);
+        const double third = FFK_PINNED(1.0/3.0);
+        const cplx m3 = {0.25*(ex.re + X*m4.im), 0.25*(ex.im - X*m4.re)};          // (e^{iX} - iX m_4)/4
+        const cplx m2 = {(ex.re + X*m3.im)*third, (ex.im - X*m3.re)*third};
+        const cplx m1 = {0.5*(ex.re + X*m2.im), 0.5*(ex.im - X*m2.re)};
+        j = derivative_integral_sum(b*dt, dt*dt, m1, m2, m3, m4);
+    }
+    return j;
+}
+
+#undef FFK_PINNED
+
 }  // namespace ffk

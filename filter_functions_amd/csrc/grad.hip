@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64) void grad_kernel(
     constexpr int U = D <= kUnrollMax ? D : 1;  // unroll (register arrays) only where they fit
     extern __shared__ unsigned char smem[];
     double* dE = reinterpret_cast<double*>(smem);          // [D2]  W_mn
-    double* inv = dE + D2;                                 // [D2]  1/W_mn, 0 where W_mn == 0
+    double* inv = dE + D2;                                 // [D2]  derivative_integral_rcp(W_mn, dt)
     cplx* Ts = reinterpret_cast<cplx*>(inv + D2);          // [D2]
     cplx* Bs = Ts + D2;                                    // [A][D2]
     cplx* As = Bs + A*D2;                                  // [H][D2]
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(64) void grad_kernel(
     for (int e = threadIdx.x; e < D2; e += 64) {
         const double v = eigvals[static_cast<size_t>(s)*D + e / D] - eigvals[static_cast<size_t>(s)*D + e % D];
         dE[e] = v;
-        inv[e] = v == 0.0 ? 0.0 : 1.0/v;
+        inv[e] = derivative_integral_rcp(v, dt[s]);
         Ts[e] = ops[static_cast<size_t>(s)*(1 + A)*D2 + e];
     }
     for (int e = threadIdx.x; e < A*D2; e += 64) Bs[e] = ops[(static_cast<size_t>(s)*(1 + A) + 1)*D2 + e];
@@ -118,17 +118,6 @@ __global__ __launch_bounds__(64) void grad_kernel(
     constexpr int LS = kLds ? 64 : 1;           // element stride of the two arrays
 #pragma unroll 1
     for (int e = 0; e < D2; ++e) I1[e*LS] = first_order_integral(om, dE[e], dts);
-    // int_0^dt tau e^{i x tau} dtau, x = w + W_e, from I1(x): the b == 0 branch of J
-    auto nested = [&](cplx i1, int e) {
-        const double x = om + dE[e];
-        const cplx ex = {1.0 - x*i1.im, x*i1.re};                  // e^{i x dt} = 1 + i x I1
-        cplx jd = {0.5*dts*dts, 0.0};
-        if (x != 0.0) {
-            const double rx = 1.0/x;
-            jd = {(dts*ex.im - i1.im)*rx, -(dts*ex.re - i1.re)*rx};   // (dt ex - I1)/(i x)
-        }
-        return jd;
-    };
     const size_t slab = static_cast<size_t>(A)*D2*W;       // one segment of Ycum
     for (int a = 0; a < A; ++a) {
         const cplx* Ytot = Ycum + static_cast<size_t>(G - 1)*slab + static_cast<size_t>(a)*D2*W + w;
@@ -217,26 +206,14 @@ __global__ __launch_bounds__(64) void grad_kernel(
 #pragma unroll U
                     for (int n = 0; n < D; ++n) {
                         // + Bbar_yn Abar_nx J(w; W_yn, W_nx)
-                        const double r1 = inv[n*D + x];
                         const cplx iyn = I1[(y*D + n)*LS];
-                        cplx j1;
-                        if (r1 != 0.0) {
-                            const cplx df = {iyx.re - iyn.re, iyx.im - iyn.im};
-                            j1 = {df.im*r1, -df.re*r1};                     // df/(i W_nx)
-                        } else {
-                            j1 = nested(iyn, y*D + n);
-                        }
+                        const cplx j1 = derivative_integral(om + dE[y*D + n], dE[n*D + x],
+                                                            inv[n*D + x], dts, iyn, iyx);
                         cmac(g, cmul(Bb[y*D + n], Ab[n*D + x]), j1);
                         // - Abar_yn Bbar_nx J(w; W_nx, W_yn)
-                        const double r2 = inv[y*D + n];
                         const cplx inx = I1[(n*D + x)*LS];
-                        cplx j2;
-                        if (r2 != 0.0) {
-                            const cplx df = {iyx.re - inx.re, iyx.im - inx.im};
-                            j2 = {df.im*r2, -df.re*r2};
-                        } else {
-                            j2 = nested(inx, n*D + x);
-                        }
+                        const cplx j2 = derivative_integral(om + dE[n*D + x], dE[y*D + n],
+                                                            inv[y*D + n], dts, inx, iyx);
                         const cplx ab = cmul(Ab[y*D + n], Bb[n*D + x]);
                         cmac(g, cplx{-ab.re, -ab.im}, j2);
                     }
@@ -268,7 +245,7 @@ __global__ __launch_bounds__(64) void grad_ctrlmat_kernel(
     constexpr int U = D <= 4 ? D : 1;
     extern __shared__ unsigned char smem[];
     double* dE = reinterpret_cast<double*>(smem);          // [D2]  W_mn
-    double* inv = dE + D2;                                 // [D2]  1/W_mn, 0 where W_mn == 0
+    double* inv = dE + D2;                                 // [D2]  derivative_integral_rcp(W_mn, dt)
     cplx* Ts = reinterpret_cast<cplx*>(inv + D2);          // [D2]
     cplx* Bs = Ts + D2;                                    // [A][D2]
     cplx* As = Bs + A*D2;                                  // [H][D2]
@@ -279,7 +256,7 @@ __global__ __launch_bounds__(64) void grad_ctrlmat_kernel(
     for (int e = threadIdx.x; e < D2; e += 64) {
         const double v = eigvals[static_cast<size_t>(s)*D + e / D] - eigvals[static_cast<size_t>(s)*D + e % D];
         dE[e] = v;
-        inv[e] = v == 0.0 ? 0.0 : 1.0/v;
+        inv[e] = derivative_integral_rcp(v, dt[s]);
         Ts[e] = ops[static_cast<size_t>(s)*(1 + A)*D2 + e];
     }
     for (int e = threadIdx.x; e < A*D2; e += 64) Bs[e] = ops[(static_cast<size_t>(s)*(1 + A) + 1)*D2 + e];
@@ -296,16 +273,6 @@ __global__ __launch_bounds__(64) void grad_ctrlmat_kernel(
     cplx I1[D2];
 #pragma unroll U
     for (int e = 0; e < D2; ++e) I1[e] = first_order_integral(om, dE[e], dts);
-    auto nested = [&](cplx i1, int e) {                    // int_0^dt tau e^{i x tau} dtau from I1(x)
-        const double x = om + dE[e];
-        const cplx ex = {1.0 - x*i1.im, x*i1.re};
-        cplx jd = {0.5*dts*dts, 0.0};
-        if (x != 0.0) {
-            const double rx = 1.0/x;
-            jd = {(dts*ex.im - i1.im)*rx, -(dts*ex.re - i1.re)*rx};
-        }
-        return jd;
-    };
     const size_t slab = static_cast<size_t>(A)*D2*W;
     for (int a = 0; a < A; ++a) {
         const cplx* Ytot = Ycum + static_cast<size_t>(G - 1)*slab + static_cast<size_t>(a)*D2*W + w;
@@ -332,25 +299,13 @@ __global__ __launch_bounds__(64) void grad_ctrlmat_kernel(
                     const cplx iyx = I1[y*D + x];
 #pragma unroll U
                     for (int n = 0; n < D; ++n) {
-                        const double r1 = inv[n*D + x];
                         const cplx iyn = I1[y*D + n];
-                        cplx j1;
-                        if (r1 != 0.0) {
-                            const cplx df = {iyx.re - iyn.re, iyx.im - iyn.im};
-                            j1 = {df.im*r1, -df.re*r1};
-                        } else {
-                            j1 = nested(iyn, y*D + n);
-                        }
+                        const cplx j1 = derivative_integral(om + dE[y*D + n], dE[n*D + x],
+                                                            inv[n*D + x], dts, iyn, iyx);
                         cmac(g, cmul(Bb[y*D + n], Ab[n*D + x]), j1);
-                        const double r2 = inv[y*D + n];
                         const cplx inx = I1[n*D + x];
-                        cplx j2;
-                        if (r2 != 0.0) {
-                            const cplx df = {iyx.re - inx.re, iyx.im - inx.im};
-                            j2 = {df.im*r2, -df.re*r2};
-                        } else {
-                            j2 = nested(inx, n*D + x);
-                        }
+                        const cplx j2 = derivative_integral(om + dE[n*D + x], dE[y*D + n],
+                                                            inv[y*D + n], dts, inx, iyx);
                         const cplx ab = cmul(Ab[y*D + n], Bb[n*D + x]);
                         cmac(g, cplx{-ab.re, -ab.im}, j2);
                     }

@@ -37,8 +37,8 @@ int grad_batch_chunk(int G, int d, int W) {
 
 namespace {
 
-// ---- record of one segment, in complex numbers: a header of 1 + d2 [as doubles: dt_s, t_s, W_mn (d2), 1/W_mn or 0
-//      where W_mn == 0 (d2)], then [T (d2)] [Bbar (A d2)] [Abar (H d2)] [E (H d2)] ------------------------------------
+// ---- record of one segment, in complex numbers: a header of 1 + d2 [as doubles: dt_s, t_s, W_mn (d2), 
+//      derivative_integral_rcp(W_mn, dt_s) (d2)], then [T (d2)] [Bbar (A d2)] [Abar (H d2)] [E (H d2)] ------------------------------------
 __host__ __device__ inline size_t record_header(int d) { return static_cast<size_t>(1 + d*d); }
 __host__ __device__ inline size_t record_elems(int d, int A, int H) {
     return record_header(d) + static_cast<size_t>(1 + A + 2*H)*d*d;
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(64) void gradb_prologue_kernel(
     if (on) {
         dE = eigvals[seg*d + m] - eigvals[seg*d + n];
         hdr[2 + e] = dE;
-        hdr[2 + d2 + e] = dE == 0.0 ? 0.0 : 1.0/dE;
+        hdr[2 + d2 + e] = derivative_integral_rcp(dE, dts);
         V[e] = eigvecs[seg*d2 + e];
         Q[e] = propagators[(static_cast<size_t>(p)*(G + 1) + s)*d2 + e];
     }
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64) void grad_batch_kernel(
     cplx* head = reinterpret_cast<cplx*>(smem);            // the record's header: dt_s, t_s,
     const double* hdr = reinterpret_cast<const double*>(smem);
     const double* dE = hdr + 2;                            // [D2]  W_mn
-    const double* inv = dE + D2;                           // [D2]  1/W_mn, 0 where W_mn == 0
+    const double* inv = dE + D2;                           // [D2]  derivative_integral_rcp(W_mn, dt)
     cplx* Ts = head + 1 + D2;                              // [D2]
     cplx* Bs = Ts + D2;                                    // [D2]   (this block's operator)
     cplx* As = Bs + D2;                                    // [H][D2]
@@ -329,17 +329,6 @@ __global__ __launch_bounds__(64) void grad_batch_kernel(
                 Wa[(x*D + y)*64] = acc;
             }
         }
-        // int_0^dt tau e^{i x tau} dtau, x = w + W_e, from I1(x): the b == 0 branch of J
-        auto nested = [&](cplx i1, int e) {
-            const double x = om + dE[e];
-            const cplx ex = {1.0 - x*i1.im, x*i1.re};                  // e^{i x dt} = 1 + i x I1
-            cplx jd = {0.5*dts*dts, 0.0};
-            if (x != 0.0) {
-                const double rx = 1.0/x;
-                jd = {(dts*ex.im - i1.im)*rx, -(dts*ex.re - i1.re)*rx};   // (dt ex - I1)/(i x)
-            }
-            return jd;
-        };
 #pragma unroll 1
         for (int h = 0; h < H; ++h) {
             const cplx* Ab = As + h*D2;
@@ -352,25 +341,13 @@ __global__ __launch_bounds__(64) void grad_batch_kernel(
                     const cplx iyx = I1[(y*D + x)*64];
 #pragma unroll
                     for (int n = 0; n < D; ++n) {
-                        const double r1 = inv[n*D + x];
                         const cplx iyn = I1[(y*D + n)*64];
-                        cplx j1;
-                        if (r1 != 0.0) {
-                            const cplx df = {iyx.re - iyn.re, iyx.im - iyn.im};
-                            j1 = {df.im*r1, -df.re*r1};
-                        } else {
-                            j1 = nested(iyn, y*D + n);
-                        }
+                        const cplx j1 = derivative_integral(om + dE[y*D + n], dE[n*D + x],
+                                                            inv[n*D + x], dts, iyn, iyx);
                         cmac(g, cmul(Bs[y*D + n], Ab[n*D + x]), j1);
-                        const double r2 = inv[y*D + n];
                         const cplx inx = I1[(n*D + x)*64];
-                        cplx j2;
-                        if (r2 != 0.0) {
-                            const cplx df = {iyx.re - inx.re, iyx.im - inx.im};
-                            j2 = {df.im*r2, -df.re*r2};
-                        } else {
-                            j2 = nested(inx, n*D + x);
-                        }
+                        const cplx j2 = derivative_integral(om + dE[n*D + x], dE[y*D + n],
+                                                            inv[y*D + n], dts, inx, iyx);
                         const cplx ab = cmul(Ab[y*D + n], Bs[n*D + x]);
                         cmac(g, cplx{-ab.re, -ab.im}, j2);
                     }

@@ -740,7 +740,14 @@ def filter_function_derivative(eigvals, eigvecs, propagators, omega, basis, n_op
            collapses to -2 Re tr(E [Y_a^dag, Ycum_{s,a}]) with Ycum the steps up to and including s
            (the part proportional to the total Y_a drops out of the real part);
       and the explicit dependence of the noise sensitivities, (n'_ah / n_a) 2 Re tr(Y_a^dag Ystep_s)
-      (:376-379)."""
+      (:376-379).
+
+    J keeps the reference's closed forms and exact-zero tests ON PURPOSE (this module restates the
+    reference): (I1(w+a+b) - I1(w+a))/(i b) for b != 0, _nested_exponential_integral for b == 0.  Next
+    to those zeros they lose eps/|b dt| resp. eps/|(w+a) dt| of dt^2/2 -- 1e-7 of a row for a segment
+    with amplitudes of 1e-9 or two levels 1e-9 apart, everything at 1e-15
+    (tests/test_gradient_exact_host.py measures it against tests/golden/gradient_exact.npz).  The
+    device kernels do not share this: csrc/ffk_math.h, derivative_integral."""
     dt = np.asarray(dt, dtype=float)
     omega = np.asarray(omega, dtype=float)
     G, d = eigvals.shape

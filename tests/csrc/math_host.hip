@@ -30,4 +30,22 @@ void ffk_host_first_order_integral_aa(long n, const double* omega, const double*
     }
 }
 
+// J(x, b) of the gradient kernels, from I1(x) and I1 at the ROUNDED sum x + b as they form it
+void ffk_host_derivative_integral(long n, const double* x, const double* b, double dt, double* out) {
+    for (long i = 0; i < n; ++i) {
+        const ffk::cplx i1x = ffk::first_order_integral(x[i], 0.0, dt);
+        const ffk::cplx i1xb = ffk::first_order_integral(x[i] + b[i], 0.0, dt);
+        ffk::cplx v = ffk::derivative_integral(x[i], b[i], ffk::derivative_integral_rcp(b[i], dt), dt,
+                                               i1x, i1xb);
+        out[2*i] = v.re;
+        out[2*i + 1] = v.im;
+    }
+}
+
+// theta: below |b dt| < theta the series replaces the divided difference
+double ffk_host_derivative_integral_band() { return ffk::kDerivativeIntegralBand; }
+
+// inside the series: |x dt| below which the moments come from their Taylor series
+double ffk_host_derivative_integral_taylor() { return ffk::kDerivativeIntegralTaylor; }
+
 }  // extern "C"

@@ -12,6 +12,10 @@ copies at the next synchronisation, time that belongs to the side that made them
   population  an optimiser's population: 64 pulses of wl.random_pulse_inputs(seed, 2, 100, 2, n_cops=2), 500
               frequencies, spectrum 1e-3/omega
   cfg2        config 2 x 16: d = 4, G = 256, A = 3, H = 3, W = 4096
+  population_idle, cfg2_idle
+              the same with the amplitudes of every second segment scaled by 1e-9 (the ends of a smooth envelope):
+              on those segments every level pair is inside the band |W_mn dt| < theta, where the nested integral comes
+              from its series (csrc/ffk_math.h, derivative_integral) and not from the divided difference
 Writes one JSON object (medians, ranges, the worst pairing of a loop time with a batched time) to --out (default
 profiles/gradients_time.json) and prints it.
 
@@ -52,7 +56,20 @@ def config2(P=16):
     return inputs, basis, omega, 1e-3/omega
 
 
-WORKLOADS = {'population': population, 'cfg2': config2}
+def idle_like(setup):
+    def scaled(P=None):
+        inputs, basis, omega, S = setup() if P is None else setup(P)
+        out = []
+        for c, cc, n, nc, dt in inputs:
+            cc = np.array(cc, dtype=float)
+            cc[:, 1::2] *= 1e-9
+            out.append((c, cc, n, nc, dt))
+        return out, basis, omega, S
+    return scaled
+
+
+WORKLOADS = {'population': population, 'cfg2': config2,
+             'population_idle': idle_like(population), 'cfg2_idle': idle_like(config2)}
 
 
 def make(inputs, basis, diagonalized):

@@ -363,6 +363,63 @@ FFK_HD cplx derivative_integral(double x, double b, double rb, double dt, cplx i
     return j;
 }
 
+// ---------------------------------------------------------------------------------------
+// The nested integral of the second-order filter function (numeric.py:170-256) is the same J:
+//     I_{ij,mn}(w) = (f(a) - f(a + b))/b = J(a, b),  f = i I1,  a = W_ij - w,  b = w + W_mn.
+// The second-order kernels contract over ij before they meet mn (second.hip), so the series comes in two
+// halves that are linear in between:
+//     m_k(a) = M_k(a)/dt^(k+1), k = 1..4                         second_order_moments, per (w, ij)
+//     J      = dt^2 sum_{k<4} (i b dt)^k/(k+1)! m_{k+1}          second_order_series, per (w, mn), of the
+//                                                                moments or of sum_ij NB_{r,ij} m_k(a_ij)
+// with derivative_integral's regimes and bounds: |b dt| >= theta the divided difference (4 u/theta of dt^2/2
+// at most), below it -- b == 0 included -- the series, whose moments come upwards from I1(a) where
+// |a dt| >= 2^-9 and from the Taylor series of m_4, downwards, below that (a == 0 included).  Inside the band
+// f(a + b) is never evaluated: the reference (and the oracle) take it at fl(W_ij + W_mn), which is not the sum
+// of the rounded a and b, and next to a resonance their numerator no longer vanishes with b.
+// ---------------------------------------------------------------------------------------
+struct SecondOrderMoments {
+    cplx m1, m2, m3, m4;
+};
+
+// i1a = I1(a)
+FFK_HD SecondOrderMoments second_order_moments(double a, double dt, cplx i1a) {
+    const double X = a*dt;
+    const cplx ex = {1.0 - a*i1a.im, a*i1a.re};                        // e^{i a dt} = 1 + i a I1
+    SecondOrderMoments m;
+    if (fabs(X) >= kDerivativeIntegralTaylor) {
+        // m_k = (e^{iX} - k m_{k-1})/(iX), m_0 = I1/dt   (dt != 0 here)
+        const double rX = 1.0/X, rdt = 1.0/dt;
+        m.m1 = {(ex.im - i1a.im*rdt)*rX, -(ex.re - i1a.re*rdt)*rX};
+        m.m2 = {(ex.im - 2.0*m.m1.im)*rX, -(ex.re - 2.0*m.m1.re)*rX};
+        m.m3 = {(ex.im - 3.0*m.m2.im)*rX, -(ex.re - 3.0*m.m2.re)*rX};
+        m.m4 = {(ex.im - 4.0*m.m3.im)*rX, -(ex.re - 4.0*m.m3.re)*rX};
+    } else {
+        // Horner S_j = 1/(j+5) + (iX/(j+1)) S_{j+1}, then k m_{k-1} = e^{iX} - iX m_k
+        m.m4 = {0.1, 0.0};                                             // j = 5
+        derivative_integral_series_step<4>(X, m.m4);
+        m.m3 = {0.25*(ex.re + X*m.m4.im), 0.25*(ex.im - X*m.m4.re)};
+        m.m2 = {(ex.re + X*m.m3.im)*(1.0/3.0), (ex.im - X*m.m3.re)*(1.0/3.0)};
+        m.m1 = {0.5*(ex.re + X*m.m2.im), 0.5*(ex.im - X*m.m2.re)};
+    }
+    return m;
+}
+
+FFK_HD cplx second_order_series(double b, double dt, cplx s1, cplx s2, cplx s3, cplx s4) {
+    return derivative_integral_sum(b*dt, dt*dt, s1, s2, s3, s4);
+}
+
+// One entry, as the kernels evaluate it; ab is the argument they use for f(a + b), fl(W_ij + W_mn).
+FFK_HD cplx second_order_integral(double a, double b, double ab, double dt) {
+    const cplx i1a = first_order_integral(a, 0.0, dt);
+    const double rb = derivative_integral_rcp(b, dt);
+    if (rb == 0.0) {
+        const SecondOrderMoments m = second_order_moments(a, dt, i1a);
+        return second_order_series(b, dt, m.m1, m.m2, m.m3, m.m4);
+    }
+    const cplx i1ab = first_order_integral(ab, 0.0, dt);
+    return {-(i1a.im - i1ab.im)*rb, (i1a.re - i1ab.re)*rb};           // (f(a) - f(ab))/b, f = (-Im I1, Re I1)
+}
+
 #undef FFK_PINNED
 
 }  // namespace ffk

@@ -16,8 +16,15 @@
 //   P_ak = sum_ij NB_{ak,ij} f(W_ij - w)        A N d^2 MACs per (g, w),
 //   M_{ak,mn} = sum_ij NB_{ak,ij} f(W_ij + W_mn)   frequency independent (so_prepare_kernel),
 // and only the second contraction, F2_{ak,bl} += sum_mn X_{ak,mn} NB_{bl,mn}, is O((A N)^2 d^2) per
-// (g, w): 8 (A N)^2 d^2 flops instead of 8 A N d^4 + 8 (A N)^2 d^2.  Entries with w + W_mn == 0
-// exactly take the limit formulas (:186-194, :241-255) through X_{ak,mn} = sum_ij NB_{ak,ij} Isp_ij.
+// (g, w): 8 (A N)^2 d^2 flops instead of 8 A N d^4 + 8 (A N)^2 d^2.
+//
+// u (P - M) divides a difference that vanishes with b = w + W_mn by b: it loses u/|b dt| of dt^2/2, and
+// M's argument fl(W_ij + W_mn) is not the sum of the rounded W_ij - w and w + W_mn, so that next to a
+// resonance the difference does not even vanish.  Where |b dt| < theta (ffk_math.h, b == 0 included)
+// the integral is expanded in b instead (second_order_moments, second_order_series):
+//   X_{ak,mn} = dt^2 sum_{k<4} (i b dt)^k/(k+1)! S^k_ak,   S^k_ak = sum_ij NB_{ak,ij} m_{k+1}(W_ij - w),
+// four row vectors per (g, w), built only where some mn of that frequency is inside the band.  The
+// reference's exact-zero tests and limit formulas (:186-194, :241-255) are the b == 0 terms of this.
 //
 // One block: a (16 RT) x (16 RT) tile of the (A N) x (A N) output for WT frequencies; the segment
 // loop runs inside the block, accumulators stay in registers, operands are staged through LDS in
@@ -89,14 +96,13 @@ __global__ __launch_bounds__(256) void so_accumulate_kernel(
     cplx* NBs = Xs + WT*mc*Tp;                  // [mc][Tp]
     cplx* frc1 = NBs + mc*Tp;                   // [WT][d2]   f(W_ij - w)
     cplx* I1 = frc1 + WT*d2;                    // [WT][d2]   e^{i w t_g} I1_ij(w)
-    cplx* Isp = I1 + WT*d2;                     // [WT][d2]   limit integrals (w + W_mn == 0)
-    cplx* P = Isp + WT*d2;                      // [WT][T]
-    cplx* Xsp = P + WT*T;                       // [WT][T]
-    cplx* GsA = Xsp + WT*T;                     // [WT][T]
+    cplx* P = I1 + WT*d2;                       // [WT][T]
+    cplx* Xsp = P + WT*T;                       // [4][WT][T] S^k, the band's moments contracted with NB
+    cplx* GsA = Xsp + 4*WT*T;                   // [WT][T]
     cplx* GsB = GsA + WT*T;                     // [WT][T]
     cplx* Gcum = GsB + WT*T;                    // [WT][T]
-    double* u = reinterpret_cast<double*>(Gcum + WT*T);   // [WT][d2]   1/(w + W_mn), 0 if special
-    int* spec = reinterpret_cast<int*>(u + WT*d2);        // [WT][d2]
+    double* u = reinterpret_cast<double*>(Gcum + WT*T);   // [WT][d2]   1/b, b = w + W_mn; b itself inside the band
+    int* spec = reinterpret_cast<int*>(u + WT*d2);        // [WT][d2]   inside the band
 
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int w0 = blockIdx.x*WT;
@@ -126,43 +132,39 @@ __global__ __launch_bounds__(256) void so_accumulate_kernel(
             const cplx fb = frac(b, dtg);
             frc1[q] = fa;
             I1[q] = cmul(cexp(w*tg), cplx{fb.im, -fb.re});     // first-order integral = -i f(b)
-            const bool sp = b == 0.0;
+            const double rb = derivative_integral_rcp(b, dtg);
+            const bool sp = rb == 0.0;
             special |= sp;
             spec[q] = sp;
-            u[q] = sp ? 0.0 : 1.0/b;
+            u[q] = sp ? b : rb;
         }
         const int any_special = __syncthreads_or(special);
-        if (any_special) {      // rare: the limit integrals of the entries with w + W_mn == 0
-            for (int q = tid; q < WT*d2; q += 256) {
-                const int wi = q / d2, e = q % d2;
-                const double a = -omega[min(w0 + wi, W - 1)] + (D[e / d] - D[e % d]);
-                cplx lim = {0.5*dtg*dtg, 0.0};
-                if (a != 0.0) {
-                    const cplx fa = frc1[q], ph = cexp(a*dtg);
-                    const double ra = 1.0/a;
-                    lim = {(fa.re + dtg*ph.im)*ra, (fa.im - dtg*ph.re)*ra};   // (f(a) - i dt e^{i a dt})/a
-                }
-                Isp[q] = lim;
-            }
-            __syncthreads();
-        }
-        // (2) per-row contractions with the d^2 scalars: P, Xsp, G^(g) for the A rows; G^(g) for the
-        // B rows
+        // (2) per-row contractions with the d^2 scalars: P, G^(g) and -- only where an mn of one of the block's
+        // frequencies is inside the band -- S^k for the A rows; G^(g) for the B rows
         if (tid < WT*2*T) {
             const int wi = tid / (2*T), side = (tid / T) & 1, r = tid % T;
             const int rowi = (side ? rowB0 : rowA0) + r;
-            cplx p = {0.0, 0.0}, gs = {0.0, 0.0}, xs = {0.0, 0.0};
+            cplx p = {0.0, 0.0}, gs = {0.0, 0.0};
+            cplx s1 = {0.0, 0.0}, s2 = {0.0, 0.0}, s3 = {0.0, 0.0}, s4 = {0.0, 0.0};
             if (rowi < AN) {
                 const cplx* nb = NB + (static_cast<size_t>(g)*AN + rowi)*d2;
                 const cplx* f1 = frc1 + wi*d2;
                 const cplx* i1 = I1 + wi*d2;
-                const cplx* is = Isp + wi*d2;
+                const double w = omega[min(w0 + wi, W - 1)];
                 for (int e = 0; e < d2; ++e) {
                     const cplx v = nb[e];
                     cmac(gs, v, i1[e]);
                     if (!side) {
-                        cmac(p, v, f1[e]);
-                        if (any_special) cmac(xs, v, is[e]);
+                        const cplx fa = f1[e];
+                        cmac(p, v, fa);
+                        if (any_special) {
+                            const double a = -w + (D[e / d] - D[e % d]);
+                            const SecondOrderMoments m = second_order_moments(a, dtg, cplx{fa.im, -fa.re});
+                            cmac(s1, v, m.m1);
+                            cmac(s2, v, m.m2);
+                            cmac(s3, v, m.m3);
+                            cmac(s4, v, m.m4);
+                        }
                     }
                 }
             }
@@ -171,7 +173,12 @@ __global__ __launch_bounds__(256) void so_accumulate_kernel(
             } else {
                 GsA[wi*T + r] = gs;
                 P[wi*T + r] = p;
-                Xsp[wi*T + r] = xs;
+                if (any_special) {
+                    Xsp[wi*T + r] = s1;
+                    Xsp[(WT + wi)*T + r] = s2;
+                    Xsp[(2*WT + wi)*T + r] = s3;
+                    Xsp[(3*WT + wi)*T + r] = s4;
+                }
             }
         }
         __syncthreads();
@@ -208,7 +215,9 @@ __global__ __launch_bounds__(256) void so_accumulate_kernel(
                     const cplx pv = P[wi*T + r];
                     const double uv = u[wi*d2 + f];
                     cplx x = {uv*(pv.re - mv.re), uv*(pv.im - mv.im)};
-                    if (spec[wi*d2 + f]) x = Xsp[wi*T + r];
+                    if (spec[wi*d2 + f])
+                        x = second_order_series(uv, dtg, Xsp[wi*T + r], Xsp[(WT + wi)*T + r],
+                                                Xsp[(2*WT + wi)*T + r], Xsp[(3*WT + wi)*T + r]);
                     if (ra >= AN) x = {0.0, 0.0};
                     Xs[(wi*mc + fl)*Tp + r] = x;
                 }
@@ -287,17 +296,16 @@ __global__ __launch_bounds__(256, 2) void so_mfma_kernel(
     cplx* Ma = NBa + RA*d2s;                        // [RA][d2s]
     cplx* NBb = Ma + RA*d2s;                        // [RB][d2s]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-    const int per_wave = 4*d2 + 3*RA + 2*RB;
+    const int per_wave = 3*d2 + 6*RA + 2*RB;        // (us and spec: one more [d2] of cplx)
     cplx* frc1 = NBb + RB*d2s + wave*per_wave;      // [d2]
     cplx* I1 = frc1 + d2;                           // [d2]
-    cplx* Isp = I1 + d2;                            // [d2]
-    cplx* P = Isp + d2;                             // [RA]
-    cplx* Xsp = P + RA;                             // [RA]
-    cplx* GsA = Xsp + RA;                           // [RA]
+    cplx* P = I1 + d2;                              // [RA]
+    cplx* Xsp = P + RA;                             // [4][RA]  S^k, the band's moments contracted with NB
+    cplx* GsA = Xsp + 4*RA;                         // [RA]
     cplx* GsB = GsA + RA;                           // [RB]
     cplx* Gcum = GsB + RB;                          // [RB]
-    double* us = reinterpret_cast<double*>(Gcum + RB);   // [d2]  1/(w + W_mn); 0 where that is singular
-    int* spec = reinterpret_cast<int*>(us + d2);         // [d2]  ... and the flag for it
+    double* us = reinterpret_cast<double*>(Gcum + RB);   // [d2]  1/b, b = w + W_mn; b itself inside the band
+    int* spec = reinterpret_cast<int*>(us + d2);         // [d2]  inside the band
 
     const int w = blockIdx.x*4 + wave;
     const double om = omega[min(w, W - 1)];
@@ -344,37 +352,34 @@ __global__ __launch_bounds__(256, 2) void so_mfma_kernel(
             const cplx fa = frac(a, dtg), fb = frac(b, dtg);
             frc1[e] = fa;
             I1[e] = cmul(cexp(om*tg), cplx{fb.im, -fb.re});      // e^{i w t_g} (-i f(b))
-            const bool sp = b == 0.0;
+            const bool sp = fabs(b*dtg) < kDerivativeIntegralBand;
             special |= sp;
             spec[e] = sp;
-            us[e] = sp ? 0.0 : rcp(b);
+            us[e] = sp ? b : rcp(b);
         }
         const bool any_special = __ballot(special) != 0ull;
-        if (any_special) {      // rare: the limit integrals of the entries with w + W_mn == 0
-            for (int e = lane; e < d2; e += 64) {
-                const double a = -om + (D[e / d] - D[e % d]);
-                cplx lim = {0.5*dtg*dtg, 0.0};
-                if (a != 0.0) {
-                    const cplx fa = frac(a, dtg), ph = cexp(a*dtg);
-                    const double ra = 1.0/a;
-                    lim = {(fa.re + dtg*ph.im)*ra, (fa.im - dtg*ph.re)*ra};
-                }
-                Isp[e] = lim;
-            }
-        }
         __syncthreads();
-        // (2) row contractions with the d^2 scalars
+        // (2) row contractions with the d^2 scalars; S^k only where an mn of this frequency is inside the band
         for (int job = lane; job < (diag ? RA : RA + RB); job += 64) {
             const bool side = job >= RA;
             const int r = side ? job - RA : job;
             const cplx* nb = (side ? NBb : NBa) + r*d2s;
-            cplx p = {0.0, 0.0}, gs = {0.0, 0.0}, xs = {0.0, 0.0};
+            cplx p = {0.0, 0.0}, gs = {0.0, 0.0};
+            cplx s1 = {0.0, 0.0}, s2 = {0.0, 0.0}, s3 = {0.0, 0.0}, s4 = {0.0, 0.0};
             for (int e = 0; e < d2; ++e) {
                 const cplx v = nb[e];
                 cmac(gs, v, I1[e]);
                 if (!side) {
-                    cmac(p, v, frc1[e]);
-                    if (any_special) cmac(xs, v, Isp[e]);
+                    const cplx fa = frc1[e];
+                    cmac(p, v, fa);
+                    if (any_special) {
+                        const double a = -om + (D[e / d] - D[e % d]);
+                        const SecondOrderMoments m = second_order_moments(a, dtg, cplx{fa.im, -fa.re});
+                        cmac(s1, v, m.m1);
+                        cmac(s2, v, m.m2);
+                        cmac(s3, v, m.m3);
+                        cmac(s4, v, m.m4);
+                    }
                 }
             }
             if (side) {
@@ -383,7 +388,12 @@ __global__ __launch_bounds__(256, 2) void so_mfma_kernel(
                 GsA[r] = gs;
                 if (diag) GsB[r] = gs;
                 P[r] = p;
-                Xsp[r] = xs;
+                if (any_special) {
+                    Xsp[r] = s1;
+                    Xsp[RA + r] = s2;
+                    Xsp[2*RA + r] = s3;
+                    Xsp[3*RA + r] = s4;
+                }
             }
         }
         wave_sync();
@@ -414,12 +424,9 @@ __global__ __launch_bounds__(256, 2) void so_mfma_kernel(
             Gcum[q].im += GsB[q].im;
         }
         // (4) incomplete interval: X . NB^T over the k-steps
-        cplx p[MT], xsp[MT];
+        cplx p[MT];
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            p[mt] = P[mt*16 + li];
-            xsp[mt] = Xsp[mt*16 + li];
-        }
+        for (int mt = 0; mt < MT; ++mt) p[mt] = P[mt*16 + li];
 #pragma unroll 1
         for (int ks = 0; ks < KS; ++ks) {
             const int mn = ks*4 + lk;
@@ -438,9 +445,11 @@ __global__ __launch_bounds__(256, 2) void so_mfma_kernel(
             for (int mt = 0; mt < MT; ++mt) {
                 const cplx m = Ma[(mt*16 + li)*d2s + e];
                 double xre = u*(p[mt].re - m.re), xim = u*(p[mt].im - m.im);
-                if (sp) {
-                    xre = xsp[mt].re;
-                    xim = xsp[mt].im;
+                if (sp) {       // u is b here
+                    const cplx* s = Xsp + mt*16 + li;
+                    const cplx x = second_order_series(u, dtg, s[0], s[RA], s[2*RA], s[3*RA]);
+                    xre = x.re;
+                    xim = x.im;
                 }
                 const double nxim = -xim;
 #pragma unroll
@@ -474,7 +483,7 @@ __global__ __launch_bounds__(256, 2) void so_mfma_kernel(
 
 size_t so_mfma_lds_bytes(int mt, int nt, int d2) {
     const size_t ra = 16*mt, rb = 16*nt;
-    return sizeof(cplx)*((2*ra + rb)*(d2 + 1) + 4*(4*size_t(d2) + 3*ra + 2*rb));
+    return sizeof(cplx)*((2*ra + rb)*(d2 + 1) + 4*(3*size_t(d2) + 6*ra + 2*rb));
 }
 
 template <int MT, int NT>
@@ -498,7 +507,7 @@ hipError_t launch_so_mfma(const double* omega, int W, const double* eigvals, con
 
 size_t so_lds_bytes(int rt, int wt, int mc, int d2) {
     const size_t T = 16*rt, Tp = T + 1;
-    return sizeof(cplx)*((wt + 1)*mc*Tp + 3*size_t(wt)*d2 + 5*size_t(wt)*T) +
+    return sizeof(cplx)*((wt + 1)*mc*Tp + 2*size_t(wt)*d2 + 8*size_t(wt)*T) +
            size_t(wt)*d2*(sizeof(double) + sizeof(int));
 }
 
@@ -747,13 +756,14 @@ hipError_t launch_second_order_filter_function(const double* omega, int W, const
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     // matrix-core kernel: the largest square wave tile (<= 48 x 48) whose operands fit in LDS twice
-    // per CU; FFK_TUNE_SO_MFMA=0 forces the vector kernel (cross-check in tests/)
+    // per CU (2 x 79 of 160 KB; at 78 the S^k rows would move d = 6 to the smaller tile);
+    // FFK_TUNE_SO_MFMA=0 forces the vector kernel (cross-check in tests/)
     bool use_mfma = true;
     if (const char* e = getenv("FFK_TUNE_SO_MFMA")) use_mfma = atoi(e) != 0;
     if (use_mfma) {
         const int tiles16 = (AN + 15)/16;
         for (int mt = min(3, tiles16); mt >= 1; --mt) {
-            if (so_mfma_lds_bytes(mt, mt, d2) > 78*1024) continue;
+            if (so_mfma_lds_bytes(mt, mt, d2) > 79*1024) continue;
             if (mt == 3) return launch_so_mfma<3, 3>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);
             if (mt == 2) return launch_so_mfma<2, 2>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);
             return launch_so_mfma<1, 1>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);

@@ -575,7 +575,13 @@ def second_order_integral(omega, eigvals_g, dt_g):
 
     with W_mn = D_m - D_n.  The reference evaluates the b == 0 rows only for w == 0 exactly
     (:241-255; for w != 0 its masked ufuncs leave the buffer untouched there); this restatement
-    applies the documented formula (:186-194) to every b == 0 entry, which coincides at w == 0."""
+    applies the documented formula (:186-194) to every b == 0 entry, which coincides at w == 0.
+
+    Known weakness, kept on purpose (this is a restatement of the reference): the limits are taken only at exact zeros,
+    so the first form loses u/|b dt| of dt^2/2 for small b != 0 and the second u/|a dt|; and f is evaluated at
+    c = fl(W_ij + W_mn), not at the sum of the rounded a and b, so that within a few ulp of a resonance the numerator
+    does not vanish with b and the entry is wrong by order one.  tests/test_second_order_exact_host.py measures both
+    against 60-digit values (oracle/make_exact_second_order.py); csrc/ffk_math.h's second_order_integral has neither."""
     E = np.asarray(omega, dtype=float)
     dE = np.subtract.outer(eigvals_g, eigvals_g)
     a = np.add.outer(-E, dE)                                    # (W,d,d)  W_ij - w

@@ -42,6 +42,16 @@ void ffk_host_derivative_integral(long n, const double* x, const double* b, doub
     }
 }
 
+// I_{ij,mn} = J(a, b) of the second-order kernels, with f(a + b) taken at ab as they take it at fl(W_ij + W_mn)
+void ffk_host_second_order_integral(long n, const double* a, const double* b, const double* ab, double dt,
+                                    double* out) {
+    for (long i = 0; i < n; ++i) {
+        ffk::cplx v = ffk::second_order_integral(a[i], b[i], ab[i], dt);
+        out[2*i] = v.re;
+        out[2*i + 1] = v.im;
+    }
+}
+
 // theta: below |b dt| < theta the series replaces the divided difference
 double ffk_host_derivative_integral_band() { return ffk::kDerivativeIntegralBand; }
 

@@ -212,6 +212,12 @@ SIGNATURES = {
     'ffk_batch_filter_function_derivative': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                                      c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                                      c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'ffk_batch_frequency_shifts_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                              c_int]),
+    'ffk_batch_frequency_shifts_chunk': (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    'ffk_batch_frequency_shifts': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                           c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                           c_int, c_void_p, c_int, c_void_p]),
     'ffk_kernel_fault_status': (c_int, [POINTER(c_int32), c_int]),
     'ffk_resident_create': (c_int, [POINTER(c_void_p)]),
     'ffk_resident_destroy': (c_int, [c_void_p]),

@@ -11,6 +11,7 @@
 //   ffk_api_frozen.hip    second order and gradient (outside SURVEY 8, frozen since round 2)
 //   ffk_api_batch.hip     many pulses of one shape in one pass of the pipeline (ffk_pipeline_batch_dev)
 //   ffk_api_batch_grad.hip  the gradient of the filter function / infidelity of many pulses in one pass
+//   ffk_api_batch_second.hip  the frequency shifts of many pulses in one pass, without F2 in memory
 #pragma once
 #include <cstdarg>
 #include <cstdio>

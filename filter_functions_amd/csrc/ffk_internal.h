@@ -158,6 +158,13 @@ hipError_t launch_apply_prologue_compact_pulses(const cplx* Qloc, const cplx* to
                                                 const double* t, int A, double* segtab, cplx* Tc, cplx* ops,
                                                 const cplx* basis, int N, void* ews, hipStream_t stream,
                                                 cplx* wfold = nullptr);
+// launch_prologue for P pulses, block (segment, pulse): every array pulse-major (propagators and t (P, G+1, ...),
+// n_opers (P,A,d,d), n_coeffs (P,A,G)); n_opers_transformed (P,A,G,d,d).  2 <= d <= 8; the noise operators
+// always ride in the one kernel.
+hipError_t launch_prologue_pulses(const double* eigvals, const cplx* eigvecs, const cplx* propagators,
+                                  const cplx* n_opers, const double* n_coeffs, const double* dt, const double* t,
+                                  int G, int P, int d, int A, double* segtab, cplx* Tc, cplx* ops,
+                                  cplx* n_opers_transformed, hipStream_t stream);
 // basis_transformed (G,N,d,d) = (Q^dag V)^dag C_k (Q^dag V)   (numeric.py:863-864)
 hipError_t launch_basis_transformed(const cplx* Tc, const cplx* basis, int G, int N, int d,
                                     cplx* out, hipStream_t stream);
@@ -397,6 +404,30 @@ hipError_t launch_second_order_filter_function(const double* omega, int W, const
                                                const double* dt, const double* t, const cplx* nt,
                                                const cplx* bt, int G, int d, int A, int N, cplx* F2,
                                                void* ws, hipStream_t stream);
+// The matrix-core kernels' square tile in units of 16 rows (1..3), 0 where none fits in LDS twice per CU and the
+// vector kernel runs: the one predicate of launch_second_order_filter_function and of the batched frequency shifts.
+int second_order_mfma_tile(int AN, int d);
+// Batched frequency shifts (ffk_batch_frequency_shifts): Delta of P pulses of one shape, F2 never in memory.
+//   so_shift_tile     the fused kernel's tile (1, 2; 0: shape not taken)
+//   so_shift_chunk    frequencies per block: a function of the shape, never of P (0: shape not taken)
+//   so_shift_plan     host side: pair_slot (A*A) = output pair of an operator pair or -1, tiles (<= T*T pairs of
+//                     tile coordinates, T = ceil(A N / (16 mt))) = the tiles that hold a selected pair; returns
+//                     their number.  idx holds distinct operators.
+int so_shift_tile(int AN, int d);
+int so_shift_chunk(int W, int N, int A, int G, int d);
+int so_shift_plan(int A, int N, int mt, int s_ndim, const int32_t* idx, int n_idx, int32_t* pair_slot,
+                  int32_t* tiles);
+// NB, M (P,G,A N,d^2) from nt (P,A,G,d,d), bt (P,G,N,d,d), eigvals (P,G,d), dt (P,G): one launch
+hipError_t launch_second_order_prepare_pulses(const double* eigvals, const double* dt, const cplx* nt,
+                                              const cplx* bt, int P, int G, int d, int A, int N, cplx* NB,
+                                              cplx* M, hipStream_t stream);
+// out (P, npairs, N, N); partial (P, ceil(W/chunk), npairs, N, N) scratch; scale from launch_spectral_weights;
+// pair_slot, tiles, ntiles from so_shift_plan (on the device).  Two launches, whatever P.
+hipError_t launch_frequency_shifts_pulses(int P, const double* omega, int W, const double* eigvals,
+                                          const double* dt, const double* t, const cplx* NB, const cplx* M, int G,
+                                          int d, int A, int N, const cplx* scale, int s_ndim,
+                                          const int32_t* pair_slot, const int32_t* tiles, int ntiles, int npairs,
+                                          double* partial, double* out, hipStream_t stream);
 // concatenation rule: F2_atomic (G,A,A,N,N,W), step (G,A,N,W) = summands of the sequence's control
 // matrix, L (G-1,N,N) f64 = Liouville matrices of the cumulative propagators -> out (A,A,N,N,W)
 size_t periodic_workspace_bytes(int A, int N, int W);

@@ -270,9 +270,10 @@ FFK_HD cplx phased_integral_aa(const PhasedFrequency& f, double dE, double sb, d
 }
 
 // exp(i x) as (cos, sin), util.py:136-162
+template <bool PIN = false>
 FFK_HD cplx cexp(double x) {
     cplx out;
-    sincos_pi(x, &out.im, &out.re);
+    sincos_pi<PIN>(x, &out.im, &out.re);
     return out;
 }
 

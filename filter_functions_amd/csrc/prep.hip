@@ -132,6 +132,34 @@ __global__ __launch_bounds__(64) void prologue_kernel(
                         ops, n_opers_transformed, eigvecs_propagated, with_noise_ops, wfold);
 }
 
+// Batched form of prologue_kernel: block (segment, pulse), every array pulse-major.
+template <int D>
+__global__ __launch_bounds__(64) void prologue_pulses_kernel(
+    const double* __restrict__ eigvals, const cplx* __restrict__ eigvecs,
+    const cplx* __restrict__ propagators, const cplx* __restrict__ n_opers,
+    const double* __restrict__ n_coeffs, const double* __restrict__ dt,
+    const double* __restrict__ t, int G, int A, double* __restrict__ segtab,
+    cplx* __restrict__ Tc, cplx* __restrict__ ops, cplx* __restrict__ n_opers_transformed) {
+    __shared__ cplx V[D][D];
+    __shared__ cplx Q[D][D];
+    __shared__ cplx T[D][D];
+    __shared__ cplx BV[D][D];
+    constexpr size_t DD = D*D;
+    const size_t p = blockIdx.y;
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x;
+    const cplx* Vp = eigvecs + p*G*DD;
+    const cplx* Qp = propagators + p*(G + 1)*DD;
+    for (int e = lane; e < D*D; e += 64) {
+        V[e / D][e % D] = Vp[static_cast<size_t>(g)*DD + e];
+        Q[e / D][e % D] = Qp[static_cast<size_t>(g)*DD + e];
+    }
+    __syncthreads();
+    prologue_segment<D>(V, Q, T, BV, g, lane, eigvals + p*G*D, n_opers + p*A*DD, n_coeffs + p*A*G, dt + p*G,
+                        t + p*(G + 1), G, A, segtab + p*G*seg_stride(D), Tc + p*G*DD, ops + p*G*(1 + A)*DD,
+                        n_opers_transformed + p*A*G*DD, nullptr, true, nullptr);
+}
+
 // Bbar_a^(g) = s_a(t_g) V_g^dag B_a V_g for one (segment, noise operator) per block.  For large d the
 // two d^3 products per operator dominate the prologue (d = 16, 18 operators: 172 us for 13 blocks
 // of one wavefront each); spread over G x A blocks they take as long as one operator.
@@ -450,6 +478,27 @@ hipError_t launch_prologue(const double* eigvals, const cplx* eigvecs, const cpl
             return hipErrorInvalidValue;
     }
     if (d == 8 && wfold != nullptr) return launch_fold_w8(segtab, ops, G, A, wfold, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_prologue_pulses(const double* eigvals, const cplx* eigvecs, const cplx* propagators,
+                                  const cplx* n_opers, const double* n_coeffs, const double* dt, const double* t,
+                                  int G, int P, int d, int A, double* segtab, cplx* Tc, cplx* ops,
+                                  cplx* n_opers_transformed, hipStream_t stream) {
+    if (P < 1 || P > 65535 || !n_opers_transformed || !n_coeffs) return hipErrorInvalidValue;
+    switch (d) {
+#define FFK_CASE(D)                                                                             \
+    case D:                                                                                     \
+        hipLaunchKernelGGL(prologue_pulses_kernel<D>, dim3(G, P), dim3(64), 0, stream, eigvals, \
+                           eigvecs, propagators, n_opers, n_coeffs, dt, t, G, A, segtab, Tc,    \
+                           ops, n_opers_transformed);                                           \
+        break;
+        // (d <= 8: from d = 9 on no tile of the matrix-core second-order kernel fits in LDS, and nothing else asks)
+        FFK_CASE(2) FFK_CASE(3) FFK_CASE(4) FFK_CASE(5) FFK_CASE(6) FFK_CASE(7) FFK_CASE(8)
+#undef FFK_CASE
+        default:
+            return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

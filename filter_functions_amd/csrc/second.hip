@@ -39,9 +39,11 @@ namespace {
 
 // (e^{i x dt} - 1)/x = (2 s / x)(-s + i c), s = sin(x dt/2), c = cos(x dt/2); i dt at x == 0
 // (util.cexpm1, util.py:165-182, divided as in numeric.py:229-235)
+// (PIN: the polynomial's constants are materialised where they are used, ffk_math.h -- the same bits)
+template <bool PIN = false>
 __device__ __forceinline__ cplx frac(double x, double dt) {
     double s, c;
-    sincos_pi(0.5*(x*dt), &s, &c);
+    sincos_pi<PIN>(0.5*(x*dt), &s, &c);
     const double q = 2.0*s*rcp(x);
     cplx out = {-q*s, q*c};
     if (x == 0.0) out = {0.0, dt};
@@ -51,37 +53,58 @@ __device__ __forceinline__ cplx frac(double x, double dt) {
 // One block per (segment g, row r = a N + k):
 //   NB[g][r][e = i d + j] = Bbar[a,g,i,j] Cbar[g,k,j,i]
 //   M[g][r][f = m d + n]  = sum_e NB[g][r][e] f(dE_e + dE_f)
-__global__ __launch_bounds__(64) void so_prepare_kernel(const cplx* __restrict__ nt,
-                                                        const cplx* __restrict__ bt,
-                                                        const double* __restrict__ eigvals,
-                                                        const double* __restrict__ dt, int G, int A,
-                                                        int N, int d, cplx* __restrict__ NB,
-                                                        cplx* __restrict__ M) {
+// B = Bbar[a,g], C = Cbar[g,k], D = the segment's eigenvalues; NBr, Mr the output rows
+__device__ __forceinline__ void so_prepare_row(const cplx* __restrict__ B, const cplx* __restrict__ C,
+                                               const double* __restrict__ D, double dtg, int d,
+                                               cplx* __restrict__ NBr, cplx* __restrict__ Mr) {
     extern __shared__ unsigned char smem[];
     const int d2 = d*d;
     cplx* row = reinterpret_cast<cplx*>(smem);                 // [d2]
     double* dE = reinterpret_cast<double*>(row + d2);          // [d2]
-    const int g = blockIdx.x, r = blockIdx.y;
-    const int a = r / N, k = r % N;
-    const cplx* B = nt + (static_cast<size_t>(a)*G + g)*d2;
-    const cplx* C = bt + (static_cast<size_t>(g)*N + k)*d2;
-    cplx* NBr = NB + (static_cast<size_t>(g)*A*N + r)*d2;
     for (int e = threadIdx.x; e < d2; e += 64) {
         const int i = e / d, j = e % d;
         const cplx v = cmul(B[e], C[j*d + i]);
         row[e] = v;
         NBr[e] = v;
-        dE[e] = eigvals[static_cast<size_t>(g)*d + i] - eigvals[static_cast<size_t>(g)*d + j];
+        dE[e] = D[i] - D[j];
     }
     __syncthreads();
-    const double dtg = dt[g];
-    cplx* Mr = M + (static_cast<size_t>(g)*A*N + r)*d2;
     for (int f = threadIdx.x; f < d2; f += 64) {
         cplx acc = {0.0, 0.0};
         const double df = dE[f];
         for (int e = 0; e < d2; ++e) cmac(acc, row[e], frac(dE[e] + df, dtg));
         Mr[f] = acc;
     }
+}
+
+__global__ __launch_bounds__(64) void so_prepare_kernel(const cplx* __restrict__ nt,
+                                                        const cplx* __restrict__ bt,
+                                                        const double* __restrict__ eigvals,
+                                                        const double* __restrict__ dt, int G, int A,
+                                                        int N, int d, cplx* __restrict__ NB,
+                                                        cplx* __restrict__ M) {
+    const int d2 = d*d;
+    const int g = blockIdx.x, r = blockIdx.y;
+    const int a = r / N, k = r % N;
+    const size_t o = (static_cast<size_t>(g)*A*N + r)*d2;
+    so_prepare_row(nt + (static_cast<size_t>(a)*G + g)*d2, bt + (static_cast<size_t>(g)*N + k)*d2,
+                   eigvals + static_cast<size_t>(g)*d, dt[g], d, NB + o, M + o);
+}
+
+// The same for P pulses, block x = p G + g: nt (P,A,G,d,d), bt (P,G,N,d,d), eigvals (P,G,d), dt (P,G) -> NB, M
+// (P,G,A N,d^2).  Only nt is not segment-major across pulses.
+__global__ __launch_bounds__(64) void so_prepare_pulses_kernel(const cplx* __restrict__ nt,
+                                                               const cplx* __restrict__ bt,
+                                                               const double* __restrict__ eigvals,
+                                                               const double* __restrict__ dt, int G, int A,
+                                                               int N, int d, cplx* __restrict__ NB,
+                                                               cplx* __restrict__ M) {
+    const int d2 = d*d;
+    const size_t pg = blockIdx.x, p = pg / G, g = pg % G;
+    const int r = blockIdx.y;
+    const int a = r / N, k = r % N;
+    const size_t o = (pg*A*N + r)*d2;
+    so_prepare_row(nt + ((p*A + a)*G + g)*d2, bt + (pg*N + k)*d2, eigvals + pg*d, dt[pg], d, NB + o, M + o);
 }
 
 template <int RT, int WT>
@@ -505,6 +528,318 @@ hipError_t launch_so_mfma(const double* omega, int W, const double* eigvals, con
     return hipGetLastError();
 }
 
+// ---- batched frequency shifts: the matrix-core pass with the spectral integral as its epilogue --------
+// Delta[p, pair, k, l] = sum_w Re(F2_p[a, b, k, l, w] scale[row(pair), w]) for P pulses of one shape, without F2 in
+// memory.  Block (x = p FB + fb, y = entry of the tile list): the segment loop of so_mfma_kernel -- the same frac,
+// second_order_moments and second_order_series calls in the same order, so one frequency's accumulators hold the
+// bits of that kernel's -- run for QB frequency quads one after the other.  After each quad a wavefront multiplies
+// its accumulators by the weighted spectrum of its frequency and adds the real parts to 4 MT NT sums it keeps in
+// registers; accumulator elements of unselected operator pairs (pair_slot < 0) are dropped.  At the end the four
+// wavefronts are added through LDS in the order 0, 1, 2, 3 and the block writes one partial per (pulse, frequency
+// block, selected pair, k, l); so_shift_reduce_kernel adds a pulse's partials in ascending frequency-block order.
+// No atomics, and nothing depends on P or on the pulse's slot: the same bits in every batch.
+// Tiles: at most 32 x 32 per wavefront.  The 48 x 48 tile of so_mfma_kernel fills the 256 registers with its
+// accumulators alone; with 36 more sums it spills.
+struct SoShiftArgs {
+    const double* omega;        // (W)
+    const double* eigvals;      // (P, G, d)
+    const double* dt;           // (P, G)
+    const double* t;            // (P, G + 1)
+    const cplx* NB;             // (P, G, A N, d^2)
+    const cplx* M;
+    const cplx* scale;          // (rows, W)
+    const int32_t* pair_slot;   // (A, A): output pair of an operator pair, -1: not selected
+    const int32_t* tiles;       // (grid.y, 2): tile row, tile column
+    double* partial;            // (P, FB, npairs, N, N)
+    int W, G, d, A, N, FB, QB, s_ndim, npairs;
+};
+
+// keeps a block-uniform value in vector registers
+template <typename T>
+__device__ __forceinline__ T in_vgpr(T x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+template <int MT, int NT>
+__global__ __launch_bounds__(256, 2) void so_shift_kernel(const SoShiftArgs k) {
+    constexpr int RA = 16*MT, RB = 16*NT;
+    const int d = k.d, d2 = d*d, d2s = d2 + 1, N = k.N, AN = k.A*N, KS = (d2 + 3)/4, W = k.W, G = k.G;
+    extern __shared__ unsigned char smem[];
+    cplx* NBa = reinterpret_cast<cplx*>(smem);      // [RA][d2s]
+    cplx* Ma = NBa + RA*d2s;                        // [RA][d2s]
+    cplx* NBb = Ma + RA*d2s;                        // [RB][d2s]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+    const int per_wave = 3*d2 + 6*RA + 2*RB;
+    cplx* frc1 = NBb + RB*d2s + wave*per_wave;      // [d2]
+    cplx* I1 = frc1 + d2;                           // [d2]
+    cplx* P = I1 + d2;                              // [RA]
+    cplx* Xsp = P + RA;                             // [4][RA]
+    cplx* GsA = Xsp + 4*RA;                         // [RA]
+    cplx* GsB = GsA + RA;                           // [RB]
+    cplx* Gcum = GsB + RB;                          // [RB]
+    double* us = reinterpret_cast<double*>(Gcum + RB);   // [d2]
+    int* spec = reinterpret_cast<int*>(us + d2);         // [d2]
+
+    const size_t pulse = blockIdx.x / k.FB;
+    const int fb = blockIdx.x % k.FB;
+    const int rowA0 = k.tiles[2*blockIdx.y]*RA, rowB0 = k.tiles[2*blockIdx.y + 1]*RB;
+    const bool diag = rowA0 == rowB0 && RA == RB;
+    const double* eigvals = k.eigvals + pulse*G*d;
+    // what only the ends of the block use, and the segment's two scalars, are held in vector registers: the
+    // segment loop has no scalar register left for them
+    const double* dts = in_vgpr(k.dt + pulse*G);
+    const double* ts = in_vgpr(k.t + pulse*(G + 1));
+    const double* omega = in_vgpr(k.omega);
+    const cplx* scale = in_vgpr(k.scale);
+    const int32_t* pair_slot = in_vgpr(k.pair_slot);
+    double* partial = in_vgpr(k.partial);
+    const int s_ndim = in_vgpr(k.s_ndim), npairs = in_vgpr(k.npairs), A = in_vgpr(k.A);
+    const cplx* NB = k.NB + pulse*G*AN*d2;
+    const cplx* M = k.M + pulse*G*AN*d2;
+
+    double sum[MT][NT][4];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sum[mt][nt][r] = 0.0;
+
+#pragma unroll 1
+    for (int qi = 0; qi < k.QB; ++qi) {
+        const int wq = (fb*k.QB + qi)*4;            // block-uniform: every wavefront leaves together
+        if (wq >= W) break;
+        const int w = wq + wave;
+        const double om = omega[min(w, W - 1)];
+        f64x4 cre[MT][NT], cim[MT][NT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                cre[mt][nt] = {0.0, 0.0, 0.0, 0.0};
+                cim[mt][nt] = {0.0, 0.0, 0.0, 0.0};
+            }
+        for (int q = lane; q < RB; q += 64) Gcum[q] = {0.0, 0.0};
+
+#pragma unroll 1
+        for (int g = 0; g < G; ++g) {
+            const double dtg = dts[g], tg = ts[g];
+            const double* D = eigvals + static_cast<size_t>(g)*d;
+            __syncthreads();                        // the previous segment's (quad's) operands are consumed
+            // (rows past A N: a row that exists is read and zero is kept -- no branch around the loads)
+            for (int q = tid; q < RA*d2; q += 256) {
+                const int r = q / d2, e = q % d2;
+                const bool in = rowA0 + r < AN;
+                const size_t o = (static_cast<size_t>(g)*AN + min(rowA0 + r, AN - 1))*d2 + e;
+                const cplx nb = NB[o], m = M[o];
+                NBa[r*d2s + e] = {in ? nb.re : 0.0, in ? nb.im : 0.0};
+                Ma[r*d2s + e] = {in ? m.re : 0.0, in ? m.im : 0.0};
+            }
+            for (int q = tid; q < RB*d2; q += 256) {
+                const int r = q / d2, e = q % d2;
+                const bool in = rowB0 + r < AN;
+                const cplx nb = NB[(static_cast<size_t>(g)*AN + min(rowB0 + r, AN - 1))*d2 + e];
+                NBb[r*d2s + e] = {in ? nb.re : 0.0, in ? nb.im : 0.0};
+            }
+            // (1) this wavefront's frequency-dependent scalars
+            bool special = false;
+            for (int e = lane; e < d2; e += 64) {
+                const double dE = D[e / d] - D[e % d];
+                const double a = -om + dE, b = om + dE;
+                const cplx fa = frac<true>(a, dtg), fb2 = frac<true>(b, dtg);
+                frc1[e] = fa;
+                I1[e] = cmul(cexp<true>(om*tg), cplx{fb2.im, -fb2.re});     // e^{i w t_g} (-i f(b))
+                const bool sp = fabs(b*dtg) < kDerivativeIntegralBand;
+                special |= sp;
+                spec[e] = sp;
+                us[e] = sp ? b : rcp(b);
+            }
+            const bool any_special = __ballot(special) != 0ull;
+            __syncthreads();
+            // (2) row contractions with the d^2 scalars; S^k only where an mn of this frequency is inside the band
+            for (int job = lane; job < (diag ? RA : RA + RB); job += 64) {
+                const bool side = job >= RA;
+                const int r = side ? job - RA : job;
+                const cplx* nb = (side ? NBb : NBa) + r*d2s;
+                cplx p = {0.0, 0.0}, gs = {0.0, 0.0};
+                cplx s1 = {0.0, 0.0}, s2 = {0.0, 0.0}, s3 = {0.0, 0.0}, s4 = {0.0, 0.0};
+                for (int e = 0; e < d2; ++e) {
+                    const cplx v = nb[e];
+                    cmac(gs, v, I1[e]);
+                    if (!side) {
+                        const cplx fa = frc1[e];
+                        cmac(p, v, fa);
+                        if (any_special) {
+                            const double a = -om + (D[e / d] - D[e % d]);
+                            const SecondOrderMoments m = second_order_moments(a, dtg, cplx{fa.im, -fa.re});
+                            cmac(s1, v, m.m1);
+                            cmac(s2, v, m.m2);
+                            cmac(s3, v, m.m3);
+                            cmac(s4, v, m.m4);
+                        }
+                    }
+                }
+                if (side) {
+                    GsB[r] = gs;
+                } else {
+                    GsA[r] = gs;
+                    if (diag) GsB[r] = gs;
+                    P[r] = p;
+                    if (any_special) {
+                        Xsp[r] = s1;
+                        Xsp[RA + r] = s2;
+                        Xsp[2*RA + r] = s3;
+                        Xsp[3*RA + r] = s4;
+                    }
+                }
+            }
+            wave_sync();
+            // (3) complete intervals: conj(G_A) x Gcum_B as a rank-one MFMA update
+            if (g > 0) {
+                double b1[NT], b2[NT];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const cplx gc = Gcum[nt*16 + li];
+                    b1[nt] = lk == 0 ? gc.re : (lk == 1 ? gc.im : 0.0);
+                    b2[nt] = lk == 0 ? gc.im : (lk == 1 ? gc.re : 0.0);
+                }
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const cplx ga = GsA[mt*16 + li];
+                    const double a1 = lk == 0 ? ga.re : (lk == 1 ? ga.im : 0.0);
+                    const double a2 = lk == 0 ? ga.re : (lk == 1 ? -ga.im : 0.0);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        cre[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1[nt], cre[mt][nt], 0, 0, 0);
+                        cim[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2[nt], cim[mt][nt], 0, 0, 0);
+                    }
+                }
+            }
+            wave_sync();
+            for (int q = lane; q < RB; q += 64) {
+                Gcum[q].re += GsB[q].re;
+                Gcum[q].im += GsB[q].im;
+            }
+            // (4) incomplete interval: X . NB^T over the k-steps
+            cplx p[MT];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) p[mt] = P[mt*16 + li];
+#pragma unroll 1
+            for (int ks = 0; ks < KS; ++ks) {
+                const int mn = ks*4 + lk;
+                const bool valid = mn < d2;
+                const int e = valid ? mn : 0;
+                const bool sp = valid && spec[e];
+                const double u = valid ? us[e] : 0.0;
+                double bre[NT], bim[NT];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const cplx v = NBb[(nt*16 + li)*d2s + e];
+                    bre[nt] = valid ? v.re : 0.0;
+                    bim[nt] = valid ? v.im : 0.0;
+                }
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const cplx m = Ma[(mt*16 + li)*d2s + e];
+                    double xre = u*(p[mt].re - m.re), xim = u*(p[mt].im - m.im);
+                    if (sp) {       // u is b here
+                        const cplx* s = Xsp + mt*16 + li;
+                        const cplx x = second_order_series(u, dtg, s[0], s[RA], s[2*RA], s[3*RA]);
+                        xre = x.re;
+                        xim = x.im;
+                    }
+                    const double nxim = -xim;
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        cre[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(xre, bre[nt], cre[mt][nt], 0, 0, 0);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        cim[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(xre, bim[nt], cim[mt][nt], 0, 0, 0);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        cre[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(nxim, bim[nt], cre[mt][nt], 0, 0, 0);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        cim[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(xim, bre[nt], cim[mt][nt], 0, 0, 0);
+                }
+            }
+        }
+        // epilogue of this frequency: sum += Re(F2 scale) for the selected pairs
+        if (w < W) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int rb = rowB0 + nt*16 + li;
+                const int b = rb < AN ? rb / N : -1;
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ra = rowA0 + mt*16 + lk + 4*r;
+                        int slot = -1;
+                        if (b >= 0 && ra < AN) slot = pair_slot[(ra / N)*A + b];
+                        if (slot >= 0) {
+                            const cplx s = scale[static_cast<size_t>(s_ndim == 1 ? 0 : slot)*W + w];
+                            sum[mt][nt][r] += cre[mt][nt][r]*s.re - cim[mt][nt][r]*s.im;
+                        }
+                    }
+            }
+        }
+    }
+    // the four wavefronts, in order, through LDS (every operand is consumed: the buffer is free)
+    double* red = reinterpret_cast<double*>(smem);  // [RA][RB]
+#pragma unroll 1
+    for (int wv = 0; wv < 4; ++wv) {
+        __syncthreads();
+        if (wave == wv) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        double* o = red + (mt*16 + lk + 4*r)*RB + nt*16 + li;
+                        *o = wv == 0 ? sum[mt][nt][r] : *o + sum[mt][nt][r];
+                    }
+        }
+    }
+    __syncthreads();
+    const size_t NN = static_cast<size_t>(N)*N;
+    double* out = partial + static_cast<size_t>(blockIdx.x)*npairs*NN;
+    for (int e = tid; e < RA*RB; e += 256) {
+        const int ra = rowA0 + e / RB, rb = rowB0 + e % RB;
+        if (ra >= AN || rb >= AN) continue;
+        const int slot = pair_slot[(ra / N)*A + rb / N];
+        if (slot >= 0) out[slot*NN + static_cast<size_t>(ra % N)*N + rb % N] = red[e];
+    }
+}
+
+// out[p, row] = sum over fb = 0 .. FB-1, in that order, of partial[p, fb, row]
+__global__ __launch_bounds__(256) void so_shift_reduce_kernel(const double* __restrict__ partial, int FB,
+                                                              size_t rows, size_t total,
+                                                              double* __restrict__ out) {
+    const size_t e = static_cast<size_t>(blockIdx.x)*256 + threadIdx.x;
+    if (e >= total) return;
+    const size_t p = e / rows, r = e % rows;
+    const double* src = partial + p*FB*rows + r;
+    double acc = 0.0;
+    for (int fb = 0; fb < FB; ++fb) acc += src[fb*rows];
+    out[e] = acc;
+}
+
+template <int MT>
+hipError_t launch_so_shift_tile(const SoShiftArgs& k, int P, int ntiles, hipStream_t stream) {
+    const size_t lds = so_mfma_lds_bytes(MT, MT, k.d*k.d);
+    auto kern = so_shift_kernel<MT, MT>;
+    if (lds > 48*1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(P)*k.FB, ntiles), dim3(256), lds, stream, k);
+    return hipGetLastError();
+}
+
 size_t so_lds_bytes(int rt, int wt, int mc, int d2) {
     const size_t T = 16*rt, Tp = T + 1;
     return sizeof(cplx)*((wt + 1)*mc*Tp + 2*size_t(wt)*d2 + 8*size_t(wt)*T) +
@@ -738,6 +1073,16 @@ hipError_t launch_second_order_from_atomic(const cplx* F2_atomic, const cplx* st
     return hipGetLastError();
 }
 
+// The matrix-core kernels' tile: the largest square wave tile (<= 48 x 48) whose operands fit in LDS twice per CU
+// (2 x 79 of 160 KB; at 78 the S^k rows would move d = 6 to the smaller tile), in units of 16 rows; 0: none fits,
+// the vector kernel runs.  The single pass and the batched frequency shifts both ask here.
+int second_order_mfma_tile(int AN, int d) {
+    const int tiles16 = (AN + 15)/16;
+    for (int mt = min(3, tiles16); mt >= 1; --mt)
+        if (so_mfma_lds_bytes(mt, mt, d*d) <= 79*1024) return mt;
+    return 0;
+}
+
 size_t second_order_workspace_bytes(int G, int A, int N, int d) {
     return 2*align_up(sizeof(cplx)*size_t(G)*A*N*d*d);
 }
@@ -755,19 +1100,15 @@ hipError_t launch_second_order_filter_function(const double* omega, int W, const
                        stream, nt, bt, eigvals, dt, G, A, N, d, NB, M);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
-    // matrix-core kernel: the largest square wave tile (<= 48 x 48) whose operands fit in LDS twice
-    // per CU (2 x 79 of 160 KB; at 78 the S^k rows would move d = 6 to the smaller tile);
-    // FFK_TUNE_SO_MFMA=0 forces the vector kernel (cross-check in tests/)
+    // matrix-core kernel where second_order_mfma_tile finds a tile; FFK_TUNE_SO_MFMA=0 forces the vector kernel
+    // (cross-check in tests/)
     bool use_mfma = true;
     if (const char* e = getenv("FFK_TUNE_SO_MFMA")) use_mfma = atoi(e) != 0;
     if (use_mfma) {
-        const int tiles16 = (AN + 15)/16;
-        for (int mt = min(3, tiles16); mt >= 1; --mt) {
-            if (so_mfma_lds_bytes(mt, mt, d2) > 79*1024) continue;
-            if (mt == 3) return launch_so_mfma<3, 3>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);
-            if (mt == 2) return launch_so_mfma<2, 2>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);
-            return launch_so_mfma<1, 1>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);
-        }
+        const int mt = second_order_mfma_tile(AN, d);
+        if (mt == 3) return launch_so_mfma<3, 3>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);
+        if (mt == 2) return launch_so_mfma<2, 2>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);
+        if (mt == 1) return launch_so_mfma<1, 1>(omega, W, eigvals, dt, t, NB, M, G, d, A, N, F2, stream);
     }
     const int rt = min(4, (AN + 15)/16);
     const int wt = W >= 512 ? 2 : 1;
@@ -800,6 +1141,80 @@ hipError_t launch_cumulant_second_order(const double* delta, size_t batch, int N
     if (batch > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(cumulant_second_order_kernel, dim3(static_cast<unsigned>(batch)), dim3(256), 0,
                        stream, delta, N, d, basis, static_cast<cplx*>(ws), K);
+    return hipGetLastError();
+}
+
+// ---- batched frequency shifts ---------------------------------------------------------------------
+int so_shift_tile(int AN, int d) {
+    int mt = min(2, second_order_mfma_tile(AN, d));
+    // FFK_TUNE_SO_SHIFT_TILE=1 forces 16 x 16 tiles (the tile measurement of DESIGN.md 7.5)
+    if (const char* e = getenv("FFK_TUNE_SO_SHIFT_TILE"))
+        if (mt > 0 && atoi(e) >= 1 && atoi(e) <= mt) mt = atoi(e);
+    return mt;
+}
+
+int so_shift_chunk(int W, int N, int A, int G, int d) {
+    if (W < 1 || N < 1 || A < 1 || G < 1 || d < 2 || d > kMaxD || second_order_mfma_tile(A*N, d) == 0) return 0;
+    return W >= 2048 ? 32 : 16;
+}
+
+int so_shift_plan(int A, int N, int mt, int s_ndim, const int32_t* idx, int n_idx, int32_t* pair_slot,
+                  int32_t* tiles) {
+    for (int q = 0; q < A*A; ++q) pair_slot[q] = -1;
+    for (int i = 0; i < n_idx; ++i) {
+        if (s_ndim == 3) {
+            for (int j = 0; j < n_idx; ++j) pair_slot[idx[i]*A + idx[j]] = i*n_idx + j;
+        } else {
+            pair_slot[idx[i]*A + idx[i]] = i;
+        }
+    }
+    const int R = 16*mt, T = (A*N + R - 1)/R;
+    int count = 0;
+    for (int ty = 0; ty < T; ++ty)
+        for (int tz = 0; tz < T; ++tz) {
+            bool wanted = false;
+            for (int a = 0; a < A && !wanted; ++a)
+                for (int b = 0; b < A && !wanted; ++b)
+                    wanted = pair_slot[a*A + b] >= 0 && a*N < (ty + 1)*R && (a + 1)*N > ty*R &&
+                             b*N < (tz + 1)*R && (b + 1)*N > tz*R;
+            if (wanted) {
+                tiles[2*count] = ty;
+                tiles[2*count + 1] = tz;
+                ++count;
+            }
+        }
+    return count;
+}
+
+hipError_t launch_second_order_prepare_pulses(const double* eigvals, const double* dt, const cplx* nt,
+                                              const cplx* bt, int P, int G, int d, int A, int N, cplx* NB,
+                                              cplx* M, hipStream_t stream) {
+    const int d2 = d*d;
+    if (A*N > 65535 || static_cast<size_t>(P)*G > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(so_prepare_pulses_kernel, dim3(static_cast<unsigned>(P)*G, A*N), dim3(64),
+                       d2*(sizeof(cplx) + sizeof(double)), stream, nt, bt, eigvals, dt, G, A, N, d, NB, M);
+    return hipGetLastError();
+}
+
+hipError_t launch_frequency_shifts_pulses(int P, const double* omega, int W, const double* eigvals,
+                                          const double* dt, const double* t, const cplx* NB, const cplx* M, int G,
+                                          int d, int A, int N, const cplx* scale, int s_ndim,
+                                          const int32_t* pair_slot, const int32_t* tiles, int ntiles, int npairs,
+                                          double* partial, double* out, hipStream_t stream) {
+    const int mt = so_shift_tile(A*N, d), chunk = so_shift_chunk(W, N, A, G, d);
+    if (mt == 0 || chunk == 0 || ntiles < 1 || ntiles > 65535 || P < 1) return hipErrorInvalidValue;
+    SoShiftArgs k;
+    k.omega = omega; k.eigvals = eigvals; k.dt = dt; k.t = t; k.NB = NB; k.M = M; k.scale = scale;
+    k.pair_slot = pair_slot; k.tiles = tiles; k.partial = partial;
+    k.W = W; k.G = G; k.d = d; k.A = A; k.N = N; k.QB = chunk/4; k.FB = (W + chunk - 1)/chunk;
+    k.s_ndim = s_ndim; k.npairs = npairs;
+    if (static_cast<size_t>(P)*k.FB > 0x7fffffffull) return hipErrorInvalidValue;
+    hipError_t err = mt == 2 ? launch_so_shift_tile<2>(k, P, ntiles, stream) : launch_so_shift_tile<1>(k, P, ntiles, stream);
+    if (err != hipSuccess) return err;
+    const size_t rows = static_cast<size_t>(npairs)*N*N, total = rows*P;
+    if ((total + 255)/256 > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(so_shift_reduce_kernel, dim3(static_cast<unsigned>((total + 255)/256)), dim3(256), 0, stream,
+                       partial, k.FB, rows, total, out);
     return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 ``ff.decay_amplitudes(pulses, S, omega)``, ``ff.cumulant_functions(pulses, S, omega)`` and
 ``ff.error_transfer_matrices(pulses, S, omega)`` are ``np.stack`` of the loops over
 ``numeric.calculate_decay_amplitudes``, ``numeric.calculate_cumulant_function`` and ``ff.error_transfer_matrix``
-(``which='total'``, first order).  A pulse whose control matrix is known on the grid -- resident in HBM behind a
+(``which='total'``; first order, or with ``second_order=True`` the frequency-shift terms of
+``ff.frequency_shifts`` added).  A pulse whose control matrix is known on the grid -- resident in HBM behind a
 :class:`~filter_functions_amd._resident.Deferred` entry after ``ff.get_filter_functions``,
 ``ff.concatenate_sequences`` or its own resident pass, or a host array -- is evaluated in batched passes: the
 resident control matrices are read where they lie (nothing is fetched, the deferred entries stay deferred), host
@@ -241,22 +242,63 @@ def decay_amplitudes(pulses, spectrum, omega, n_oper_identifiers=None):
     function inside the call: correct results, the caches as the loop leaves them, no speed-up.
 
     Input order is kept.  The pulses must agree on the number of selected noise operators and of basis elements
-    (else ValueError); an empty list gives an empty float array.  Pulse correlations, second order and
-    precomputed inputs are not offered: use the single functions.
+    (else ValueError); an empty list gives an empty float array.  Pulse correlations and precomputed inputs are not
+    offered: use the single functions.
     """
     return _results('decay_amplitudes', pulses, spectrum, omega, n_oper_identifiers)
 
 
-def cumulant_functions(pulses, spectrum, omega, n_oper_identifiers=None):
+def _second_order_cumulants(pulses, spectrum, omega, n_oper_identifiers):
+    """First-order cumulant functions from the batched pass, frequency shifts from ``ff.frequency_shifts``, and
+    the second-order term of all pulses (of one basis) added by one call of ``ffk_cumulant_function_second_order``:
+    what ``numeric.calculate_cumulant_function(..., second_order=True)`` does for one pulse."""
+    from .batch_second_order import _same_basis, frequency_shifts
+    pulses = list(pulses)
+    K = _results('cumulant_function', pulses, spectrum, omega, n_oper_identifiers)
+    if not pulses:
+        return K
+    delta = frequency_shifts(pulses, spectrum, omega, n_oper_identifiers)
+    if np.shape(delta) != np.shape(K):
+        raise ValueError('Frequency shifts not same shape as decay amplitudes')
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    todo = list(range(len(pulses)))
+    while todo:
+        basis = pulses[todo[0]].basis
+        same = [i for i in todo if _same_basis(basis, pulses[i].basis)]
+        todo = [i for i in todo if i not in same]
+        N, d = np.shape(basis)[:2]
+        numeric._check_d(d)
+        C = as_c128(np.asarray(basis))
+        part = np.ascontiguousarray(K[same]).reshape(-1, N, N)
+        shifts = np.ascontiguousarray(as_f64(delta[same]).reshape(-1, N, N))
+        check(_lib.load().ffk_cumulant_function_second_order(shifts.ctypes.data, len(shifts), N, d, C.ctypes.data,
+                                                             part.ctypes.data))
+        K[same] = part.reshape((len(same),) + K.shape[1:])
+    return K
+
+
+def cumulant_functions(pulses, spectrum, omega, n_oper_identifiers=None, second_order=False):
     r"""Cumulant functions :math:`\mathcal{K}_{\alpha\beta}` of many pulses, same shape as
     :func:`decay_amplitudes`: ``np.stack([numeric.calculate_cumulant_function(p, spectrum, omega,
-    n_oper_identifiers) for p in pulses])``.  Routing, shapes and exceptions as :func:`decay_amplitudes`."""
+    n_oper_identifiers, second_order=second_order) for p in pulses])``.  Routing, shapes and exceptions as
+    :func:`decay_amplitudes`.  With *second_order* the frequency shifts come from :func:`ff.frequency_shifts
+    <filter_functions_amd.batch_second_order.frequency_shifts>` (whose routing and caches apply) and their
+    contribution to every pulse's cumulant function is added in one call."""
+    if second_order:
+        return _second_order_cumulants(pulses, spectrum, omega, n_oper_identifiers)
     return _results('cumulant_function', pulses, spectrum, omega, n_oper_identifiers)
 
 
-def error_transfer_matrices(pulses, spectrum, omega, n_oper_identifiers=None):
+def error_transfer_matrices(pulses, spectrum, omega, n_oper_identifiers=None, second_order=False):
     r"""Error transfer matrices :math:`\exp\mathcal{K}` of many pulses, shape (n_pulses, N, N):
-    ``np.stack([ff.error_transfer_matrix(p, spectrum, omega, n_oper_identifiers) for p in pulses])``.  The sum
-    over the noise operators, the norm, the choice of the squarings and the exponential run on the device, one
-    wavefront per pulse.  Routing, shapes and exceptions as :func:`decay_amplitudes`."""
+    ``np.stack([ff.error_transfer_matrix(p, spectrum, omega, n_oper_identifiers, second_order=second_order) for p in
+    pulses])``.  The sum over the noise operators, the norm, the choice of the squarings and the exponential run on
+    the device, one wavefront per pulse.  Routing, shapes and exceptions as :func:`decay_amplitudes`.  With
+    *second_order* the cumulant functions are those of :func:`cumulant_functions` with ``second_order=True``, each
+    exponentiated as ``ff.error_transfer_matrix(cumulant_function=...)`` does."""
+    if second_order:
+        K = _second_order_cumulants(pulses, spectrum, omega, n_oper_identifiers)
+        if not len(K):
+            return K
+        return np.stack([numeric.error_transfer_matrix(cumulant_function=k) for k in K])
     return _results('error_transfer_matrix', pulses, spectrum, omega, n_oper_identifiers)

@@ -541,6 +541,27 @@ int ffk_batch_filter_function_derivative(int P, const double* eigvals, const dou
                                          int s_ndim, double* filter_function_derivative,
                                          double* infidelity_derivative);
 
+/* ffk_frequency_shifts_from_scratch for P pulses of one shape at once, 1 <= P <= 65535, without the second-order
+ * filter function in memory.  Per-pulse arrays are pulse-major with a leading axis P, as in
+ * ffk_batch_filter_function_derivative; omega (W,), basis (N, d, d), spectrum ((W,), (n_idx, W) or (n_idx, n_idx, W)
+ * c128) and idx (n_idx distinct noise operators) are shared.  frequency_shifts (P, n_idx, N, N) f64, or
+ * (P, n_idx, n_idx, N, N) for s_ndim 3.  Shapes: those for which the single pass runs its matrix-core kernel (a square
+ * wave tile whose operands fit in LDS twice per CU); others are refused, ..._workspace_bytes and ..._chunk return 0.
+ * The pass runs that kernel's segment loop and integrates each frequency's accumulators against the weighted
+ * spectrum in its epilogue; only the tiles of the (A N) x (A N) output that hold a selected operator pair are
+ * launched.  A block walks ffk_batch_frequency_shifts_chunk(W, N, A, G, d) frequencies and writes one partial; a
+ * second kernel adds a pulse's partials in ascending order, without atomics.  The chunk depends on the shape only,
+ * never on P: a pulse's result is the same bits in every batch and at every slot.  Every input array crosses in one
+ * copy, the result in one copy, nothing synchronises in between, and the number of launches and copies does not
+ * depend on P.  The two queries run without a GPU; ..._workspace_bytes is exactly linear in P.                    */
+size_t ffk_batch_frequency_shifts_workspace_bytes(int P, int W, int N, int A, int G, int d, int n_idx, int s_ndim);
+int ffk_batch_frequency_shifts_chunk(int W, int N, int A, int G, int d);
+int ffk_batch_frequency_shifts(int P, const double* eigvals, const double* eigvecs, const double* propagators,
+                               const double* omega, int W, const double* basis, int N, const double* n_opers, int A,
+                               const double* n_coeffs, const double* dt, const double* t, int G, int d,
+                               const double* spectrum, int s_ndim, const int32_t* idx, int n_idx,
+                               double* frequency_shifts);
+
 /* Fault word of the kernels whose wavefronts hand tiles to one another through flags in LDS (the d = 4
  * accumulation behind ffk_control_matrix*, ffk_pipeline_dev and the resident passes; reference loop
  * numeric.py:846-869).  Their waits are bounded; a wait that runs out stores a non-zero code in a word of mapped

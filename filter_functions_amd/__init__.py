@@ -13,12 +13,13 @@ The arithmetic runs in hand-written HIP kernels for gfx950 behind a C ABI
 side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
-from . import (analytic, basis, batch, batch_gradient, batch_second_order, gradient, numeric, processes, pulse_sequence, sequences,
+from . import (analytic, basis, batch, batch_gradient, batch_second_order, correlations, gradient, numeric, processes, pulse_sequence, sequences,
                superoperator, util)
 from .basis import Basis
 from .batch import get_filter_functions, infidelities
 from .batch_gradient import filter_function_derivatives, infidelity_derivatives
 from .batch_second_order import frequency_shifts
+from .correlations import correlation_infidelities
 from .gradient import infidelity_derivative
 from .numeric import error_transfer_matrix, infidelity
 from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
@@ -31,6 +32,7 @@ __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradie
            'concatenate',
            'concatenate_periodic',
            'concatenate_sequences',
+           'correlation_infidelities', 'correlations',
            'concatenate_without_filter_function', 'cumulant_functions', 'decay_amplitudes',
            'error_transfer_matrices', 'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
            'filter_function_derivatives', 'frequency_shifts', 'infidelity_derivative', 'infidelity_derivatives',

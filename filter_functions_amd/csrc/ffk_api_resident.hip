@@ -1089,6 +1089,166 @@ int ffk_resident_batch_infidelity(ffk_resident* r, const int32_t* members, int n
     return FFK_OK;
 }
 
+// ---- pulse-correlation infidelities of many sequences from one gate table in ONE pass
+//      (ff.correlation_infidelities; correlations.hip) ------------------------------------------------------------
+namespace {
+
+struct CorrLayout {
+    size_t offsets, index, out_offsets, members, tau, omega, basis, U, tab, host, S, idx, inputs_end;   // one H2D
+    size_t infid, outputs_end;                                                                          // one D2H
+    size_t Q, phases, L, Qc, scale, part, end;                                                          // device only
+};
+
+// total: the sum of G_p^2 (the rows of the ragged output)
+CorrLayout corr_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W, SpectrumShape sh,
+                       int n_idx, size_t total) {
+    CorrLayout L;
+    const size_t dd = size_t(d)*d;
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.offsets = put(4*(size_t(P) + 1));
+    L.index = put(4*n_index);
+    L.out_offsets = put(8*(size_t(P) + 1));
+    L.members = put(4*size_t(P));
+    L.tau = put(8*size_t(T));
+    L.omega = put(8*size_t(W));
+    L.basis = put(16*size_t(N)*dd);
+    L.U = put(16*size_t(T)*dd);
+    L.tab = put(8*size_t(T));
+    L.host = put(16*size_t(A)*N*W*size_t(n_host));
+    L.S = put(16*sh.rows*W);
+    L.idx = put(4*size_t(n_idx));
+    L.inputs_end = o;
+    L.infid = put(8*total*n_idx);
+    L.outputs_end = o;
+    L.Q = put(16*size_t(P)*dd);
+    L.phases = put(16*size_t(T)*W);
+    L.L = put(8*size_t(T)*N*N);
+    L.Qc = put(8*n_index*N*N);
+    L.scale = put(16*sh.rows*W);
+    L.part = put(8*size_t(ffk::correlation_slabs(W, nullptr))*n_idx*total);
+    L.end = o;
+    return L;
+}
+
+bool corr_shape_ok(int T, int P, int d, int A, int N, int W, int n_idx, int s_ndim) {
+    return T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && ffk::sequences_supported(d, N, A) && W >= 1 &&
+           (s_ndim == 1 || s_ndim == 2) && n_idx >= 1 && n_idx <= A;
+}
+
+}  // namespace
+
+size_t ffk_sequence_correlation_infidelities_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A,
+                                                             int N, int W, int n_idx, int s_ndim) {
+    if (!corr_shape_ok(T, P, d, A, N, W, n_idx, s_ndim) || n_index < P || n_host < 0 || n_host > T) return 0;
+    // the lengths are not known here: no sequence is longer than the cap or than all positions together
+    const size_t longest = std::min(size_t(ffk::correlation_max_length()), size_t(n_index));
+    return corr_layout(T, P, size_t(n_index), n_host, d, A, N, W, spectrum_shape(s_ndim, n_idx), n_idx,
+                       size_t(n_index)*longest).end;
+}
+
+int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                          const double* gate_propagators, const double* tau, int T,
+                                          const int32_t* offsets, const int32_t* index, int P, const double* omega,
+                                          int W, const double* basis, int hermitian_basis, int d, int A, int N,
+                                          const double* spectrum, int s_ndim, int spectrum_is_real, const int32_t* idx,
+                                          int n_idx, int d_infidelity, const int64_t* out_offsets, double* infidelity) {
+    FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis && spectrum && idx &&
+                out_offsets && infidelity, "NULL argument");
+    FFK_REQUIRE(ffk::sequences_supported(d, N, A), "unsupported shape d=%d N=%d A=%d (need d = 2, N = 4, 1 <= A <= 4)",
+                d, N, A);
+    FFK_REQUIRE(hermitian_basis != 0, "the batched pass needs a Hermitian basis");
+    FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
+    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 1,
+                "empty or oversized axis: T=%d P=%d W=%d", T, P, W);
+    if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d_infidelity, W >= 2)) return rc;
+    const int max_length = ffk::correlation_max_length();
+    FFK_REQUIRE(offsets[0] == 0 && out_offsets[0] == 0, "offsets[0] = %d, out_offsets[0] = %lld, expected 0",
+                offsets[0], static_cast<long long>(out_offsets[0]));
+    for (int p = 0; p < P; ++p) {
+        const int64_t G = int64_t(offsets[p + 1]) - offsets[p];
+        FFK_REQUIRE(G >= 1 && G <= max_length, "sequence %d has %lld positions, need 1 ... %d", p,
+                    static_cast<long long>(G), max_length);
+        FFK_REQUIRE(out_offsets[p + 1] - out_offsets[p] == G*G, "out_offsets is not the prefix sum of G^2 at sequence %d",
+                    p);
+    }
+    const size_t n_index = size_t(offsets[P]), total = size_t(out_offsets[P]);
+    for (size_t g = 0; g < n_index; ++g)
+        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
+    if (s_ndim <= 2 && !spectrum_is_real)
+        for (size_t i = 0; i < spectrum_shape(s_ndim, n_idx).rows*W; ++i)
+            FFK_REQUIRE(spectrum[2*i + 1] == 0.0, "the spectrum has an imaginary part at element %zu", i);
+    const SpectrumShape sh = spectrum_shape(s_ndim, n_idx);
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    std::vector<const unsigned char*> tab;
+    int n_host = 0;
+    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
+    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    const CorrLayout L = corr_layout(T, P, n_index, n_host, d, A, N, W, sh, n_idx, total);
+    const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
+    // the sequences sorted by the length class whose kernel serves them (stable), and how many of each
+    std::vector<int32_t> members(P);
+    int class_counts[4] = {0, 0, 0, 0};
+    for (int p = 0; p < P; ++p) {
+        members[p] = p;
+        ++class_counts[ffk::correlation_class(offsets[p + 1] - offsets[p])];
+    }
+    std::stable_sort(members.begin(), members.end(), [offsets](int32_t a, int32_t b) {
+        return ffk::correlation_class(offsets[a + 1] - offsets[a]) < ffk::correlation_class(offsets[b + 1] - offsets[b]);
+    });
+    PinLease pin;
+    if (int rc = pin.take(L.outputs_end, dev)) return rc;
+    unsigned char* hp = pin.ptr();
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    void* base = nullptr;
+    if (int rc = arena_reserve(L.end, &base)) return rc;
+    unsigned char* dp = static_cast<unsigned char*>(base);
+    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
+    std::memcpy(hp + L.index, index, 4*n_index);
+    std::memcpy(hp + L.out_offsets, out_offsets, 8*(size_t(P) + 1));
+    std::memcpy(hp + L.members, members.data(), 4*size_t(P));
+    std::memcpy(hp + L.tau, tau, 8*size_t(T));
+    std::memcpy(hp + L.omega, omega, 8*size_t(W));
+    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
+    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
+    place_host_rows(&tab, dp + L.host, row);
+    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
+    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp + L.S, hp + L.idx);
+    StreamDrain drain{s};
+    auto at = [dp](size_t off) { return dp + off; };
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
+    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.index));
+    const int64_t* dOut = reinterpret_cast<const int64_t*>(at(L.out_offsets));
+    const double* dOmega = reinterpret_cast<const double*>(at(L.omega));
+    cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
+    double* dL = reinterpret_cast<double*>(at(L.L));
+    double* dQc = reinterpret_cast<double*>(at(L.Qc));
+    cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
+    double* dPart = reinterpret_cast<double*>(at(L.part));
+    FFK_HIP(ffk::launch_sequences_front(reinterpret_cast<const cplx*>(at(L.U)), reinterpret_cast<const double*>(at(L.tau)),
+                                        dOmega, T, W, dOff, dIdx, P, reinterpret_cast<const cplx*>(at(L.basis)), dPh,
+                                        dL, reinterpret_cast<cplx*>(at(L.Q)), s));
+    FFK_HIP(ffk::launch_correlation_prefix(dL, dOff, dIdx, P, dQc, s));
+    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(sh.rows), W, dOmega, W, 0, dScale,
+                                         s));
+    FFK_HIP(ffk::launch_correlation_gram(dPh, reinterpret_cast<const cplx* const*>(at(L.tab)), dQc, dOff, dIdx, dOut,
+                                         reinterpret_cast<const int32_t*>(at(L.members)), class_counts, W, dScale,
+                                         s_ndim, reinterpret_cast<const int32_t*>(at(L.idx)), n_idx, d_infidelity,
+                                         int64_t(total), dPart, s));
+    FFK_HIP(ffk::launch_correlation_reduce(dPart, dOut, dOff, P, n_idx, W, int64_t(total),
+                                           reinterpret_cast<double*>(at(L.infid)), s));
+    FFK_HIP(hipMemcpyAsync(hp + L.infid, dp + L.infid, 8*total*n_idx, hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    if (int rc = kernel_fault_status()) return rc;
+    std::memcpy(infidelity, hp + L.infid, 8*total*n_idx);
+    return FFK_OK;
+}
+
 // ---- decay amplitudes, cumulant functions and error transfer matrices of many pulses in ONE pass, their control
 //      matrices read where they lie in HBM (ff.decay_amplitudes, ff.cumulant_functions, ff.error_transfer_matrices;
 //      processes.hip) ----------------------------------------------------------------------------------------------
@@ -1409,6 +1569,15 @@ extern "C" int ffk_selftest_host(int rounds, unsigned seed, char* report, int re
             if (!ascending(SL) || SL.L + 8*size_t(T)*16 > SL.end ||
                 SL.end != ffk_concatenate_sequences_workspace_bytes(T, P, n_index, n_host, 2, As, 4, W, si, s_ndim))
                 return -14;
+            // the correlation pass: the workspace query bounds the layout of any lengths of at most 256 positions
+            const int sc = pick(1, 2);
+            const size_t longest = std::min(size_t(n_index - P + 1), size_t(256));
+            const size_t total = longest*longest + size_t(P - 1);      // one sequence as long as can be, the rest of 1
+            const CorrLayout CL = corr_layout(T, P, size_t(n_index), n_host, 2, As, 4, W, spectrum_shape(sc, si), si, total);
+            if (n_index - P + 1 <= 256 &&
+                (!ascending(CL) || CL.part + 8*size_t(ffk::correlation_slabs(W, nullptr))*si*total > CL.end ||
+                 CL.end > ffk_sequence_correlation_infidelities_workspace_bytes(T, P, n_index, n_host, 2, As, 4, W, si, sc)))
+                return -16;
             const int Np = N < 16 ? N : 16, hosts = pick(0, P);
             const ProcLayout PL = proc_layout(P, hosts, A, Np, W, d, n_idx, s_ndim, false, true, true, true);
             if (!ascending(PL) || PL.end != ffk_resident_batch_processes_workspace_bytes(P, hosts, A, Np, W, d, n_idx, s_ndim))

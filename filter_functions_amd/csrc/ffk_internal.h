@@ -378,6 +378,26 @@ hipError_t launch_sequences_rule(const cplx* phases, const cplx* const* Rtab, co
                                  const int32_t* offsets, const int32_t* index, const int32_t* order, int P, int T,
                                  int A, int W, cplx* R, cplx* F, hipStream_t stream);
 
+// ---- correlations.hip -------------------------------------------------------------------------
+// Pulse-correlation infidelities of many sequences from one gate table (d = 2, N = 4, A <= 4, at most
+// correlation_max_length() positions each), after launch_sequences_front.  Prefix: Qc (n_index, N, N) f64, the
+// Liouville propagator accumulated BEFORE each position.  Gram: members (P) the sequences sorted by
+// correlation_class of their length, class_counts (4) how many of each; scale from launch_spectral_weights (s_ndim
+// 1: one row, 2: one row per selected operator); part (correlation_slabs(W), n_idx, total) f64 with total =
+// out_offsets[P] = sum of G_p^2.  Reduce: out (total, n_idx), the slabs added in index order.
+int correlation_max_length();
+int correlation_class(int G);
+int correlation_slabs(int W, int* width);
+hipError_t launch_correlation_prefix(const double* Lpulse, const int32_t* offsets, const int32_t* index, int P,
+                                     double* Qc, hipStream_t stream);
+hipError_t launch_correlation_gram(const cplx* phases, const cplx* const* Rtab, const double* Qc,
+                                   const int32_t* offsets, const int32_t* index, const int64_t* out_offsets,
+                                   const int32_t* members, const int* class_counts, int W, const cplx* scale,
+                                   int s_ndim, const int32_t* idx, int n_idx, int d, int64_t total, double* part,
+                                   hipStream_t stream);
+hipError_t launch_correlation_reduce(const double* part, const int64_t* out_offsets, const int32_t* offsets, int P,
+                                     int n_idx, int W, int64_t total, double* out, hipStream_t stream);
+
 // ---- decay.hip -------------------------------------------------------------------------------
 // Gamma (Gp,Gp,n_idx[,n_idx],N,N) f64 from R (Gp,A,N,W) c128 (Gp = 1: the total control matrix),
 // S c128 (W,), (n_idx,W) or (n_idx,n_idx,W); omega (Wg,) is the global grid of which R and S hold

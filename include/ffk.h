@@ -680,6 +680,31 @@ int ffk_resident_batch_infidelity(ffk_resident* handle, const int32_t* members, 
                                   int s_ndim, int spectrum_is_real, const int32_t* idx, int n_idx, int d,
                                   double* infidelity);
 
+/* ---- pulse-correlation infidelities of many gate sequences in ONE pass (ff.correlation_infidelities) ----
+ * I[g, h, a] of sequence p, the contribution of its gate pair (g, h) to its infidelity on noise operator idx[a]:
+ * (1 / 2 pi d_infidelity) times the trapezoid integral of S_a(w) Re sum_k conj(X_g[a, k, w]) X_h[a, k, w] over the
+ * summands X_g = e^{i w t_{g-1}} v_{k_g} Q^{(g-1)} of the concatenation rule.  Sequences, gates, gate_table,
+ * gate_propagators, tau, omega and basis as for ffk_concatenate_sequences_resident (d = 2, N = 4, 1 <= A <= 4,
+ * Hermitian basis); every sequence has 1 ... 256 positions.  spectrum (W,) (s_ndim = 1) or (n_idx, W) (s_ndim = 2),
+ * f64 if spectrum_is_real, else c128 with a zero imaginary part; cross-spectra (s_ndim = 3) are FFK_EINVAL.  idx
+ * (n_idx,) int32 in [0, A); W >= 2.  out_offsets (P + 1) int64 host: the prefix sums of G_p^2; infidelity
+ * (out_offsets[P], n_idx) f64 host: sequence p's (G_p, G_p, n_idx) array starts at row out_offsets[p].  There is no
+ * result handle: one H2D copy, five to eight launches whatever P (one Gram launch per class of lengths that has
+ * members: up to 32, 64, 128, 256 positions), one D2H copy.  Neither the summands nor the pulse-correlation filter function (G, G, A, A, W) are formed: each
+ * block generates the summands of a few frequencies in LDS and accumulates the real Gram matrix of the positions on
+ * the FP64 matrix cores; the frequency axis is cut into slabs that depend on W alone and are added in index order,
+ * the lower triangle is the mirror of the upper.  A sequence's result is the same bits whatever else is in the pass.
+ * The workspace query needs no GPU; it bounds the arena bytes of any lengths (0: unsupported shape).  Bad arguments:
+ * FFK_EINVAL before anything touches the device. */
+size_t ffk_sequence_correlation_infidelities_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A,
+                                                             int N, int W, int n_idx, int s_ndim);
+int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                          const double* gate_propagators, const double* tau, int T,
+                                          const int32_t* offsets, const int32_t* index, int P, const double* omega,
+                                          int W, const double* basis, int hermitian_basis, int d, int A, int N,
+                                          const double* spectrum, int s_ndim, int spectrum_is_real, const int32_t* idx,
+                                          int n_idx, int d_infidelity, const int64_t* out_offsets, double* infidelity);
+
 /* ---- decay amplitudes, cumulant functions and error transfer matrices of P independent pulses in ONE pass
  *      (ff.decay_amplitudes, ff.cumulant_functions, ff.error_transfer_matrices) ----
  * The control matrix (A, N, W) of pulse p is read in place: pulses[p] an ffk_resident* with slots[p] < 0 for a

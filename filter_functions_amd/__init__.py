@@ -24,6 +24,7 @@ from .gradient import infidelity_derivative
 from .numeric import error_transfer_matrix, infidelity
 from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
 from .sequences import concatenate_sequences
+from .sequence_infidelities import sequence_infidelities
 from .pulse_sequence import (PulseSequence, concatenate, concatenate_periodic,
                              concatenate_without_filter_function, extend, remap)
 from .superoperator import liouville_representation
@@ -37,6 +38,6 @@ __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradie
            'error_transfer_matrices', 'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
            'filter_function_derivatives', 'frequency_shifts', 'infidelity_derivative', 'infidelity_derivatives',
            'liouville_representation', 'numeric', 'processes',
-           'pulse_sequence', 'remap', 'sequences', 'superoperator', 'util']
+           'pulse_sequence', 'remap', 'sequence_infidelities', 'sequences', 'superoperator', 'util']
 
 __version__ = '0.1.0'

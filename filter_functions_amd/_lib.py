@@ -264,6 +264,11 @@ SIGNATURES = {
                                                       c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                                       c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                                       c_int, c_void_p, c_void_p]),
+    'ffk_sequence_infidelities_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                             c_int, c_int]),
+    'ffk_sequence_infidelities': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                          c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'ffk_resident_batch_processes_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                                 c_int]),
     'ffk_resident_batch_processes': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

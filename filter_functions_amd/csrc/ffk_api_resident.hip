@@ -1249,6 +1249,158 @@ int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int3
     return FFK_OK;
 }
 
+// ---- infidelities of many sequences from one gate table in ONE pass, single- or two-qubit gates
+//      (ff.sequence_infidelities; sequences.hip, sequences_d4.hip) ------------------------------------------------
+namespace {
+
+struct SeqInfidLayout {
+    size_t offsets, index, order, tau, omega, basis, U, tab, host, S, idx, inputs_end;    // one H2D
+    size_t infid, Q, small_outputs_end, F, outputs_end;                                   // one D2H (F if asked for)
+    size_t phases, L, end;                                                                // device only
+};
+
+SeqInfidLayout seq_infid_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W, SpectrumShape sh,
+                                int n_idx) {
+    SeqInfidLayout L;
+    const size_t dd = size_t(d)*d;
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.offsets = put(4*(size_t(P) + 1));
+    L.index = put(4*n_index);
+    L.order = put(4*size_t(P));
+    L.tau = put(8*size_t(T));
+    L.omega = put(8*size_t(W));
+    L.basis = put(16*size_t(N)*dd);
+    L.U = put(16*size_t(T)*dd);
+    L.tab = put(8*size_t(T));
+    L.host = put(16*size_t(A)*N*W*size_t(n_host));
+    L.S = put(16*sh.rows*W);
+    L.idx = put(4*size_t(n_idx));
+    L.inputs_end = o;
+    L.infid = put(8*size_t(P)*sh.n_out);
+    L.Q = put(16*size_t(P)*dd);
+    L.small_outputs_end = o;
+    L.F = put(16*size_t(P)*A*A*W);
+    L.outputs_end = o;
+    L.phases = put(16*size_t(T)*W);
+    L.L = put(8*size_t(T)*N*N);
+    L.end = o;
+    return L;
+}
+
+bool seq_infid_shape_ok(int T, int P, int d, int A, int N, int W) {
+    return T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 1 &&
+           (ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A));
+}
+
+}  // namespace
+
+size_t ffk_sequence_infidelities_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                                 int n_idx, int s_ndim) {
+    if (!seq_infid_shape_ok(T, P, d, A, N, W) || n_index < P || n_host < 0 || n_host > T) return 0;
+    if (s_ndim != 0 && (s_ndim < 1 || s_ndim > 3 || n_idx < 1 || n_idx > A)) return 0;
+    return seq_infid_layout(T, P, size_t(n_index), n_host, d, A, N, W,
+                            s_ndim ? spectrum_shape(s_ndim, n_idx) : SpectrumShape{}, s_ndim ? n_idx : 0).end;
+}
+
+int ffk_sequence_infidelities(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                              const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                              const int32_t* index, int P, const double* omega, int W, const double* basis,
+                              int hermitian_basis, int d, int A, int N, const double* spectrum, int s_ndim,
+                              int spectrum_is_real, const int32_t* idx, int n_idx, int d_infidelity,
+                              double* infidelity, double* total_propagators, double* filter_function) {
+    FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis, "NULL argument");
+    FFK_REQUIRE(spectrum ? infidelity != nullptr : (total_propagators || filter_function),
+                "NULL output argument: a spectrum needs infidelity, no spectrum another output");
+    FFK_REQUIRE(ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A),
+                "unsupported shape d=%d N=%d A=%d (need (d, N) = (2, 4) or (4, 16), 1 <= A <= 4)", d, N, A);
+    FFK_REQUIRE(hermitian_basis != 0, "the batched rule needs a Hermitian basis");
+    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 1,
+                "empty or oversized axis: T=%d P=%d W=%d", T, P, W);
+    FFK_REQUIRE(offsets[0] == 0, "offsets[0] = %d, expected 0", offsets[0]);
+    for (int p = 0; p < P; ++p)
+        FFK_REQUIRE(offsets[p + 1] > offsets[p], "offsets not increasing at sequence %d (%d -> %d)", p, offsets[p],
+                    offsets[p + 1]);
+    const size_t n_index = size_t(offsets[P]);
+    for (size_t g = 0; g < n_index; ++g)
+        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
+    if (spectrum) {
+        if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d_infidelity, W >= 2)) return rc;
+        FFK_REQUIRE(P <= 65535, "the integral takes at most 65535 sequences per pass, got %d", P);
+    } else {
+        n_idx = 0;
+    }
+    const SpectrumShape sh = spectrum ? spectrum_shape(s_ndim, n_idx) : SpectrumShape{};
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    std::vector<const unsigned char*> tab;
+    int n_host = 0;
+    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
+    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    const SeqInfidLayout L = seq_infid_layout(T, P, n_index, n_host, d, A, N, W, sh, n_idx);
+    const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
+    const size_t copied_end = filter_function ? L.outputs_end : L.small_outputs_end;
+    // the sequences sorted by length, longest first (stable): the rule kernels deal them out in this order
+    std::vector<int32_t> order(P);
+    for (int p = 0; p < P; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [offsets](int32_t a, int32_t b) {
+        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
+    });
+    PinLease pin;
+    if (int rc = pin.take(copied_end, dev)) return rc;
+    unsigned char* hp = pin.ptr();
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    void* base = nullptr;
+    if (int rc = arena_reserve(L.end, &base)) return rc;
+    unsigned char* dp = static_cast<unsigned char*>(base);
+    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
+    std::memcpy(hp + L.index, index, 4*n_index);
+    std::memcpy(hp + L.order, order.data(), 4*size_t(P));
+    std::memcpy(hp + L.tau, tau, 8*size_t(T));
+    std::memcpy(hp + L.omega, omega, 8*size_t(W));
+    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
+    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
+    place_host_rows(&tab, dp + L.host, row);
+    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
+    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    if (spectrum) stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp + L.S, hp + L.idx);
+    StreamDrain drain{s};
+    auto at = [dp](size_t off) { return dp + off; };
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    const cplx* dU = reinterpret_cast<const cplx*>(at(L.U));
+    const double* dTau = reinterpret_cast<const double*>(at(L.tau));
+    const double* dOmega = reinterpret_cast<const double*>(at(L.omega));
+    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
+    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.index));
+    const int32_t* dOrder = reinterpret_cast<const int32_t*>(at(L.order));
+    const cplx* dBasis = reinterpret_cast<const cplx*>(at(L.basis));
+    const cplx* const* dTab = reinterpret_cast<const cplx* const*>(at(L.tab));
+    cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
+    double* dL = reinterpret_cast<double*>(at(L.L));
+    cplx* dQ = reinterpret_cast<cplx*>(at(L.Q));
+    cplx* dF = reinterpret_cast<cplx*>(at(L.F));
+    if (d == 2) {
+        FFK_HIP(ffk::launch_sequences_front(dU, dTau, dOmega, T, W, dOff, dIdx, P, dBasis, dPh, dL, dQ, s));
+        FFK_HIP(ffk::launch_sequences_rule(dPh, dTab, dL, dOff, dIdx, dOrder, P, T, A, W, nullptr, dF, s));
+    } else {
+        FFK_HIP(ffk::launch_sequences4_front(dU, dTau, dOmega, T, W, dOff, dIdx, P, dBasis, dPh, dL, dQ, s));
+        FFK_HIP(ffk::launch_sequences4_rule(dPh, dTab, dL, dOff, dIdx, dOrder, P, T, A, W, dF, s));
+    }
+    if (spectrum)
+        FFK_HIP(ffk::launch_infidelity_pulses(dF, A, W, P, reinterpret_cast<const cplx*>(at(L.S)), s_ndim, dOmega,
+                                              reinterpret_cast<const int32_t*>(at(L.idx)), n_idx, d_infidelity,
+                                              reinterpret_cast<double*>(at(L.infid)), s));
+    FFK_HIP(hipMemcpyAsync(hp + L.infid, dp + L.infid, copied_end - L.infid, hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    if (int rc = kernel_fault_status()) return rc;
+    if (spectrum) std::memcpy(infidelity, hp + L.infid, 8*size_t(P)*sh.n_out);
+    if (total_propagators) std::memcpy(total_propagators, hp + L.Q, 16*size_t(P)*dd);
+    if (filter_function) std::memcpy(filter_function, hp + L.F, 16*size_t(P)*A*A*W);
+    return FFK_OK;
+}
+
 // ---- decay amplitudes, cumulant functions and error transfer matrices of many pulses in ONE pass, their control
 //      matrices read where they lie in HBM (ff.decay_amplitudes, ff.cumulant_functions, ff.error_transfer_matrices;
 //      processes.hip) ----------------------------------------------------------------------------------------------

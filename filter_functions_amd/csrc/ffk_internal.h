@@ -378,6 +378,18 @@ hipError_t launch_sequences_rule(const cplx* phases, const cplx* const* Rtab, co
                                  const int32_t* offsets, const int32_t* index, const int32_t* order, int P, int T,
                                  int A, int W, cplx* R, cplx* F, hipStream_t stream);
 
+// ---- sequences_d4.hip -------------------------------------------------------------------------
+// The same pass for two-qubit gates (d = 4, N = 16, A <= 4): Lpulse (T, 16, 16), Qtot (P, 4, 4); the rule runs on the
+// FP64 matrix cores and writes F (P, A, A, W) only.  (launch_sequences_rule with R == NULL writes F only as well.)
+bool sequences4_supported(int d, int N, int A);
+bool sequences4_staged(int T, int A);
+hipError_t launch_sequences4_front(const cplx* U, const double* tau, const double* omega, int T, int W,
+                                   const int32_t* offsets, const int32_t* index, int P, const cplx* basis,
+                                   cplx* phases, double* Lpulse, cplx* Qtot, hipStream_t stream);
+hipError_t launch_sequences4_rule(const cplx* phases, const cplx* const* Rtab, const double* Lpulse,
+                                  const int32_t* offsets, const int32_t* index, const int32_t* order, int P, int T,
+                                  int A, int W, cplx* F, hipStream_t stream);
+
 // ---- correlations.hip -------------------------------------------------------------------------
 // Pulse-correlation infidelities of many sequences from one gate table (d = 2, N = 4, A <= 4, at most
 // correlation_max_length() positions each), after launch_sequences_front.  Prefix: Qc (n_index, N, N) f64, the

@@ -190,9 +190,12 @@ __global__ __launch_bounds__(STAGED ? 64*seq_staged_waves(A) : 64*kSeqGlobalWave
             }
         }
         if (w < W) {
-            cplx* Rp = R + static_cast<size_t>(p)*ROWS*W + w;
+            // (R == NULL: ffk_sequence_infidelities keeps the filter function only)
+            if (R) {
+                cplx* Rp = R + static_cast<size_t>(p)*ROWS*W + w;
 #pragma unroll
-            for (int e = 0; e < ROWS; ++e) Rp[static_cast<size_t>(e)*W] = S[e];
+                for (int e = 0; e < ROWS; ++e) Rp[static_cast<size_t>(e)*W] = S[e];
+            }
             // F[a,b] = sum_k conj(R[a,k]) R[b,k] with the arithmetic of ff_fidelity_kernel (a <= b, mirrored,
             // diagonal imaginary part 0)
             cplx* Fp = F + static_cast<size_t>(p)*A*A*W + w;

@@ -705,6 +705,28 @@ int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int3
                                           const double* spectrum, int s_ndim, int spectrum_is_real, const int32_t* idx,
                                           int n_idx, int d_infidelity, const int64_t* out_offsets, double* infidelity);
 
+/* ---- infidelities of many gate sequences from one gate set in ONE pass (ff.sequence_infidelities) ----
+ * infidelity (P, n_idx) f64 host, or (P, n_idx, n_idx) for s_ndim = 3: what ffk_concatenate_sequences_resident
+ * returns as `infidelity`, without a result handle and without the sequences' control matrices, which this entry
+ * never writes to memory; the filter functions (P, A, A, W) exist in the arena workspace only.  Sequences, gates,
+ * slots, gate_table, gate_propagators, tau, omega, basis, spectrum, idx and d_infidelity as there (Hermitian basis;
+ * with a spectrum W >= 2 and P <= 65535).  Supported: (d, N) = (2, 4) and (4, 16), 1 <= A <= 4.  Optional outputs, each
+ * may be NULL: total_propagators (P, d, d) c128 host, filter_function (P, A, A, W) c128 host (owned by the caller);
+ * spectrum may be NULL if one of them is asked for (infidelity is then not written).  One H2D copy, three launches
+ * whatever P -- phases, Liouville propagators and total propagators; the rule with the filter function; the
+ * integral --, one D2H copy.  d = 2 runs the kernels and the arithmetic of ffk_concatenate_sequences_resident; d = 4
+ * runs the 16 x 16 product of the recurrence on the FP64 matrix cores.  A sequence's result is the same bits
+ * whatever else is in the pass and whatever its place.  The workspace query needs no GPU (0: unsupported shape; s_ndim
+ * = 0: no spectrum).  Bad arguments: FFK_EINVAL before anything touches the device. */
+size_t ffk_sequence_infidelities_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                                 int n_idx, int s_ndim);
+int ffk_sequence_infidelities(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                              const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                              const int32_t* index, int P, const double* omega, int W, const double* basis,
+                              int hermitian_basis, int d, int A, int N, const double* spectrum, int s_ndim,
+                              int spectrum_is_real, const int32_t* idx, int n_idx, int d_infidelity,
+                              double* infidelity, double* total_propagators, double* filter_function);
+
 /* ---- decay amplitudes, cumulant functions and error transfer matrices of P independent pulses in ONE pass
  *      (ff.decay_amplitudes, ff.cumulant_functions, ff.error_transfer_matrices) ----
  * The control matrix (A, N, W) of pulse p is read in place: pulses[p] an ffk_resident* with slots[p] < 0 for a

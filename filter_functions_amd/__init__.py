@@ -14,7 +14,7 @@ side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
 from . import (analytic, basis, batch, batch_gradient, batch_second_order, correlations, gradient, numeric, processes, pulse_sequence, sequences,
-               superoperator, util)
+               sequence_processes, superoperator, util)
 from .basis import Basis
 from .batch import get_filter_functions, infidelities
 from .batch_gradient import filter_function_derivatives, infidelity_derivatives
@@ -25,6 +25,8 @@ from .numeric import error_transfer_matrix, infidelity
 from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
 from .sequences import concatenate_sequences
 from .sequence_infidelities import sequence_infidelities
+from .sequence_processes import (sequence_cumulant_functions, sequence_decay_amplitudes,
+                                 sequence_error_transfer_matrices)
 from .pulse_sequence import (PulseSequence, concatenate, concatenate_periodic,
                              concatenate_without_filter_function, extend, remap)
 from .superoperator import liouville_representation
@@ -38,6 +40,8 @@ __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradie
            'error_transfer_matrices', 'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
            'filter_function_derivatives', 'frequency_shifts', 'infidelity_derivative', 'infidelity_derivatives',
            'liouville_representation', 'numeric', 'processes',
-           'pulse_sequence', 'remap', 'sequence_infidelities', 'sequences', 'superoperator', 'util']
+           'pulse_sequence', 'remap', 'sequence_cumulant_functions', 'sequence_decay_amplitudes',
+           'sequence_error_transfer_matrices', 'sequence_infidelities', 'sequence_processes', 'sequences',
+           'superoperator', 'util']
 
 __version__ = '0.1.0'

@@ -1541,6 +1541,178 @@ int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slo
     return FFK_OK;
 }
 
+// ---- decay amplitudes, cumulant functions and error transfer matrices of many sequences from one gate table in ONE
+//      pass, under any number of spectra (ff.sequence_decay_amplitudes, ...; sequence_processes.hip) ----------------
+namespace {
+
+struct SeqProcLayout {
+    size_t offsets, index, order, tau, omega, basis, U, tab, host, S, idx, inputs_end;    // one H2D
+    size_t out, flags, Q, outputs_end;                                                    // one D2H
+    size_t phases, L, scale, partial, gamma, K, cumulant, end;                            // device only
+};
+
+// stage: 1 decay amplitudes, 2 cumulant function, 3 error transfer matrix (the requested one lies in `out`)
+SeqProcLayout seq_proc_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W, int n_idx,
+                              int s_ndim, int n_spectra, int stage, bool single_qubit) {
+    SeqProcLayout L;
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N;
+    const size_t rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
+    const size_t tiles = size_t(n_spectra)*P*n_idx;
+    const int width = ffk::sequence_processes_block_width(d, A);
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.offsets = put(4*(size_t(P) + 1));
+    L.index = put(4*n_index);
+    L.order = put(4*size_t(P));
+    L.tau = put(8*size_t(T));
+    L.omega = put(8*size_t(W));
+    L.basis = put(16*size_t(N)*dd);
+    L.U = put(16*size_t(T)*dd);
+    L.tab = put(8*size_t(T));
+    L.host = put(16*size_t(A)*N*W*size_t(n_host));
+    L.S = put(16*rows*W);
+    L.idx = put(4*size_t(n_idx));
+    L.inputs_end = o;
+    L.out = put(stage == 3 ? 8*size_t(n_spectra)*P*nn : 8*tiles*nn);
+    L.flags = put(4*size_t(n_spectra)*P);
+    L.Q = put(16*size_t(P)*dd);
+    L.outputs_end = o;
+    L.phases = put(16*size_t(T)*W);
+    L.L = put(8*size_t(T)*nn);
+    L.scale = put(16*rows*W);
+    L.partial = put(8*size_t((W + width - 1)/width)*tiles*nn);
+    L.gamma = stage == 1 ? L.out : put(8*tiles*nn);
+    L.K = stage == 2 ? L.out : put(stage == 3 ? 8*tiles*nn : 0);
+    L.cumulant = put(stage >= 2 && !single_qubit ? ffk::cumulant_workspace_bytes(tiles, N, d) : 0);
+    L.end = o;
+    return L;
+}
+
+bool seq_proc_shape_ok(int T, int P, int d, int A, int N, int W, int n_idx, int s_ndim, int n_spectra, int stage) {
+    return seq_infid_shape_ok(T, P, d, A, N, W) && W >= 2 && (s_ndim == 1 || s_ndim == 2) && n_idx >= 1 &&
+           n_idx <= A && n_spectra >= 1 && n_spectra <= 65535 && stage >= 1 && stage <= 3;
+}
+
+}  // namespace
+
+size_t ffk_sequence_processes_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                              int n_idx, int s_ndim, int n_spectra, int stage) {
+    if (!seq_proc_shape_ok(T, P, d, A, N, W, n_idx, s_ndim, n_spectra, stage) || n_index < P || n_host < 0 ||
+        n_host > T)
+        return 0;
+    return seq_proc_layout(T, P, size_t(n_index), n_host, d, A, N, W, n_idx, s_ndim, n_spectra, stage, false).end;
+}
+
+int ffk_sequence_processes(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                           const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                           const int32_t* index, int P, const double* omega, int W, const double* basis,
+                           int hermitian_basis, int d, int A, int N, int single_qubit, const double* spectrum,
+                           int s_ndim, int n_spectra, const int32_t* idx, int n_idx, int stage, double* out,
+                           int32_t* not_finite, double* total_propagators) {
+    FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis && spectrum && idx &&
+                out && not_finite, "NULL argument");
+    FFK_REQUIRE(ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A),
+                "unsupported shape d=%d N=%d A=%d (need (d, N) = (2, 4) or (4, 16), 1 <= A <= 4)", d, N, A);
+    FFK_REQUIRE(hermitian_basis != 0, "the batched rule needs a Hermitian basis");
+    FFK_REQUIRE(!single_qubit || d == 2, "single-qubit expression needs d = 2, N = 4");
+    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 2,
+                "empty or oversized axis: T=%d P=%d W=%d (need W >= 2)", T, P, W);
+    FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
+    FFK_REQUIRE(n_spectra >= 1 && n_spectra <= 65535, "n_spectra = %d, need 1 ... 65535", n_spectra);
+    FFK_REQUIRE(stage >= 1 && stage <= 3, "stage = %d, need 1 (decay amplitudes), 2 (cumulant function) or 3 (error "
+                "transfer matrix)", stage);
+    if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d, true)) return rc;
+    FFK_REQUIRE(offsets[0] == 0, "offsets[0] = %d, expected 0", offsets[0]);
+    for (int p = 0; p < P; ++p)
+        FFK_REQUIRE(offsets[p + 1] > offsets[p], "offsets not increasing at sequence %d (%d -> %d)", p, offsets[p],
+                    offsets[p + 1]);
+    const size_t n_index = size_t(offsets[P]);
+    for (size_t g = 0; g < n_index; ++g)
+        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
+    const size_t tiles = size_t(n_spectra)*P*n_idx, members = size_t(n_spectra)*P;
+    FFK_REQUIRE(tiles <= (size_t(1) << 26), "%zu decay-amplitude tiles exceed one pass", tiles);
+    FFK_REQUIRE(stage < 2 || single_qubit || tiles <= 65535,
+                "%d spectra x %d sequences x %d operators exceed the 65535 cumulant functions of one launch",
+                n_spectra, P, n_idx);
+    const size_t s_rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    std::vector<const unsigned char*> tab;
+    int n_host = 0;
+    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
+    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    const SeqProcLayout L = seq_proc_layout(T, P, n_index, n_host, d, A, N, W, n_idx, s_ndim, n_spectra, stage,
+                                            single_qubit != 0);
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N, row = 16*size_t(A)*N*W;
+    const size_t out_bytes = stage == 3 ? 8*members*nn : 8*tiles*nn;
+    // the sequences sorted by length, longest first (stable): the kernels deal them out in this order
+    std::vector<int32_t> order(P);
+    for (int p = 0; p < P; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [offsets](int32_t a, int32_t b) {
+        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
+    });
+    PinLease pin;
+    if (int rc = pin.take(L.outputs_end, dev)) return rc;
+    unsigned char* hp = pin.ptr();
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    void* base = nullptr;
+    if (int rc = arena_reserve(L.end, &base)) return rc;
+    unsigned char* dp = static_cast<unsigned char*>(base);
+    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
+    std::memcpy(hp + L.index, index, 4*n_index);
+    std::memcpy(hp + L.order, order.data(), 4*size_t(P));
+    std::memcpy(hp + L.tau, tau, 8*size_t(T));
+    std::memcpy(hp + L.omega, omega, 8*size_t(W));
+    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
+    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
+    place_host_rows(&tab, dp + L.host, row);
+    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
+    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    stage_spectrum(spectrum, true, s_rows*W, idx, n_idx, hp + L.S, hp + L.idx);
+    StreamDrain drain{s};
+    auto at = [dp](size_t off) { return dp + off; };
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    const cplx* dU = reinterpret_cast<const cplx*>(at(L.U));
+    const double* dTau = reinterpret_cast<const double*>(at(L.tau));
+    const double* dOmega = reinterpret_cast<const double*>(at(L.omega));
+    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
+    const int32_t* dIndex = reinterpret_cast<const int32_t*>(at(L.index));
+    const int32_t* dOrder = reinterpret_cast<const int32_t*>(at(L.order));
+    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.idx));
+    const cplx* dBasis = reinterpret_cast<const cplx*>(at(L.basis));
+    const cplx* const* dTab = reinterpret_cast<const cplx* const*>(at(L.tab));
+    cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
+    double* dL = reinterpret_cast<double*>(at(L.L));
+    cplx* dQ = reinterpret_cast<cplx*>(at(L.Q));
+    cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
+    double* dGamma = reinterpret_cast<double*>(at(L.gamma));
+    double* dK = reinterpret_cast<double*>(at(L.K));
+    int32_t* dFlags = reinterpret_cast<int32_t*>(at(L.flags));
+    FFK_HIP(hipMemsetAsync(dFlags, 0, 4*members, s));
+    if (d == 2)
+        FFK_HIP(ffk::launch_sequences_front(dU, dTau, dOmega, T, W, dOff, dIndex, P, dBasis, dPh, dL, dQ, s));
+    else
+        FFK_HIP(ffk::launch_sequences4_front(dU, dTau, dOmega, T, W, dOff, dIndex, P, dBasis, dPh, dL, dQ, s));
+    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(s_rows), W, dOmega, W, 0, dScale,
+                                         s));
+    FFK_HIP(ffk::launch_sequences_gamma(d, dPh, dTab, dL, dOff, dIndex, dOrder, P, T, A, W, dScale, s_ndim, n_spectra,
+                                        dIdx, n_idx, reinterpret_cast<double*>(at(L.partial)), dGamma, s));
+    if (stage >= 2)
+        FFK_HIP(ffk::launch_cumulant_function(dGamma, tiles, N, d, dBasis, single_qubit, dK, at(L.cumulant), s));
+    if (stage >= 3)
+        FFK_HIP(ffk::launch_processes_expm(dK, int(members), n_idx, N, reinterpret_cast<double*>(at(L.out)), dFlags,
+                                           s));
+    FFK_HIP(hipMemcpyAsync(hp + L.out, dp + L.out, L.outputs_end - L.out, hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    if (int rc = kernel_fault_status()) return rc;
+    std::memcpy(out, hp + L.out, out_bytes);
+    std::memcpy(not_finite, hp + L.flags, 4*members);
+    if (total_propagators) std::memcpy(total_propagators, hp + L.Q, 16*size_t(P)*dd);
+    return FFK_OK;
+}
+
 }  // extern "C"
 
 #if defined(FFK_HOST_SANITIZE)

@@ -383,12 +383,26 @@ hipError_t launch_sequences_rule(const cplx* phases, const cplx* const* Rtab, co
 // FP64 matrix cores and writes F (P, A, A, W) only.  (launch_sequences_rule with R == NULL writes F only as well.)
 bool sequences4_supported(int d, int N, int A);
 bool sequences4_staged(int T, int A);
+int sequences4_groups(int P, int W, int A, bool staged);
 hipError_t launch_sequences4_front(const cplx* U, const double* tau, const double* omega, int T, int W,
                                    const int32_t* offsets, const int32_t* index, int P, const cplx* basis,
                                    cplx* phases, double* Lpulse, cplx* Qtot, hipStream_t stream);
 hipError_t launch_sequences4_rule(const cplx* phases, const cplx* const* Rtab, const double* Lpulse,
                                   const int32_t* offsets, const int32_t* index, const int32_t* order, int P, int T,
                                   int A, int W, cplx* F, hipStream_t stream);
+
+// ---- sequence_processes.hip -------------------------------------------------------------------
+// Decay amplitudes of the sequences of such a pass (d = 2 or 4), after the front launch of its dimension: the rule's
+// walk with Gamma formed from its registers, then the frequency blocks' partial tiles added in index order (two
+// launches whatever P and n_spectra).  scale from launch_spectral_weights: (n_spectra, W) for s_ndim = 1,
+// (n_spectra, n_idx, W) for s_ndim = 2, real weights.  partial (ceil(W / block width), P, n_spectra, n_idx, N, N) f64
+// scratch; gamma (n_spectra, P, n_idx, N, N) f64.  The block width depends on d and A alone.
+int sequence_processes_block_width(int d, int A);
+bool sequence_processes_staged(int d, int T, int A);
+hipError_t launch_sequences_gamma(int d, const cplx* phases, const cplx* const* Rtab, const double* Lpulse,
+                                  const int32_t* offsets, const int32_t* index, const int32_t* order, int P, int T,
+                                  int A, int W, const cplx* scale, int s_ndim, int n_spectra, const int32_t* idx,
+                                  int n_idx, double* partial, double* gamma, hipStream_t stream);
 
 // ---- correlations.hip -------------------------------------------------------------------------
 // Pulse-correlation infidelities of many sequences from one gate table (d = 2, N = 4, A <= 4, at most

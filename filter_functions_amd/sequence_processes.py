@@ -1,0 +1,265 @@
+"""Quantum processes of many gate sequences given as index arrays into one gate set (``ffk_sequence_processes``,
+include/ffk.h).
+
+``ff.sequence_decay_amplitudes(gates, sequences, spectrum, omega)``, ``ff.sequence_cumulant_functions(...)`` and
+``ff.sequence_error_transfer_matrices(...)`` are ``np.stack`` of the loops over ``numeric.calculate_decay_amplitudes``,
+``numeric.calculate_cumulant_function`` and ``ff.error_transfer_matrix`` on ``ff.concatenate(gates[s], omega=omega)``:
+the index-array front end of :mod:`~filter_functions_amd.sequence_infidelities` for the batched processes of
+:mod:`~filter_functions_amd.processes`.  On the batched route no ``PulseSequence`` is built for a sequence and the
+sequences' control matrices are never written to memory: the decay amplitudes are formed from the registers of the
+concatenation-rule kernel at the end of each sequence, for every spectrum of the call (``stacked=True``) in one walk of
+the sequences.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib, util
+from ._lib import as_c128, as_f64, check
+from .batch import MAX_PULSES, PASS_BYTES, split_passes
+from .processes import _single
+from .sequence_infidelities import _on_grid, eligibility, index_arrays
+from .sequences import pack_sequences, resident_source
+
+__all__ = ['sequence_decay_amplitudes', 'sequence_cumulant_functions', 'sequence_error_transfer_matrices']
+
+_STAGES = {'decay_amplitudes': 1, 'cumulant_function': 2, 'error_transfer_matrix': 3}
+#: Cumulant functions of one launch at most (unless the single-qubit expression serves them).
+MAX_CUMULANTS = 65535
+
+
+def block_width(d, A):
+    """Frequencies of one block of the rule kernel (``sequence_processes_block_width``): a function of d and A alone."""
+    return 64 if d == 2 or A <= 2 else 32
+
+
+def _up(nbytes):
+    return -(-nbytes//256)*256
+
+
+def pass_bytes(max_length, d, A, W, n_idx, n_spectra):
+    """Device bytes one sequence adds to a pass at most: its positions, propagator, flags, its tiles of the decay
+    amplitudes, the cumulant function and the result, the frequency blocks' partial tiles and the workspace of its
+    cumulant functions."""
+    N, dd = d*d, d*d
+    tiles = n_spectra*n_idx
+    blocks = -(-W//block_width(d, A))
+    cumulant = tiles*(2*_up(16*N*dd) + 2*_up(16*dd*dd))
+    return 8 + 4*max_length + 16*dd + 4*n_spectra + 8*N*N*tiles*(3 + blocks) + cumulant
+
+
+def table_bytes(n_gates, d, A, W, n_idx, n_spectra, s_ndim):
+    """Device bytes of what a pass holds once whatever its sequences: the gate table, the gates' phases, propagators
+    and Liouville representations, the spectra and their weights, the basis and its lists."""
+    N, dd = d*d, d*d
+    rows = n_spectra*(1 if s_ndim == 1 else n_idx)
+    lists = _up(4) + _up(4*N) + _up(4*N*dd) + _up(16*N*dd) + _up(4*dd) + _up(4*dd*N) + _up(16*dd*N)
+    return (n_gates*(16*A*N*W + 16*W + 8*N*N + 16*dd + 16) + 16*N*dd + 8*W + 32*rows*W + 4*n_idx + lists
+            + 32*256)
+
+
+def max_sequences(n_idx, n_spectra, stage, single_qubit):
+    """Sequences one pass can hold whatever their size: the cumulant functions of a pass share one launch."""
+    if _STAGES[stage] == 1 or single_qubit:
+        return MAX_PULSES
+    return max(1, min(MAX_PULSES, MAX_CUMULANTS//(n_spectra*n_idx)))
+
+
+def stacked_spectra(spectrum, stacked):
+    """The spectra of the call as a list of arrays and whether a leading axis was taken off: ``[spectrum]``, or with
+    *stacked* ``spectrum[k]`` for every k of the leading axis ((K, W), (K, n_idx, W) or (K, n_idx, n_idx, W))."""
+    spectrum = np.asanyarray(spectrum)
+    if not stacked:
+        return [spectrum]
+    if spectrum.ndim not in (2, 3, 4):
+        raise ValueError('With stacked=True the spectrum needs a leading axis of K spectra: shape (K, n_omega), '
+                         f'(K, n_idx, n_omega) or (K, n_idx, n_idx, n_omega), not {spectrum.shape}.')
+    if len(spectrum) == 0:
+        raise ValueError('With stacked=True the spectrum needs at least one spectrum along its leading axis.')
+    return [spectrum[k] for k in range(len(spectrum))]
+
+
+def _real_weights(parsed):
+    """The parsed spectra as one float array (K, ...) if the batched route takes them -- one or two dimensions, no
+    imaginary part --, else None."""
+    if any(S.ndim not in (1, 2) for S in parsed):
+        return None
+    if any(np.iscomplexobj(S) and np.any(np.imag(S) != 0) for S in parsed):
+        return None
+    return as_f64(np.stack([np.real(S) for S in parsed]))
+
+
+def _run_pass(gates, indices, plan, omega, S, idx, stage, want_U):
+    """One call of ``ffk_sequence_processes`` over the sequences *indices* (int32 arrays into *gates*) and the spectra
+    S (K, W) or (K, n_idx, W): (values (K, P, ...), not finite (K, P), total propagators (P, d, d) or None)."""
+    d, N, A = plan['d'], plan['N'], plan['A']
+    W, P, K = len(omega), len(indices), len(S)
+    used = np.unique(np.concatenate(indices))
+    slot_of = np.full(len(gates), -1, dtype=np.int32)
+    slot_of[used] = np.arange(len(used), dtype=np.int32)
+    table_gates = [gates[k] for k in used]
+    sources = [resident_source(g, d, W, N, A) for g in table_gates]
+    host = [g for g, src in zip(table_gates, sources) if src is None]
+    table = as_c128(np.array([g.get_control_matrix(omega) for g in host])) if host else None
+    handles = (ctypes.c_void_p*len(table_gates))(*[None if src is None else src[0].value for src in sources])
+    slots = np.array([-1 if src is None else src[1] for src in sources], dtype=np.int32)
+    U = as_c128(np.array([g.total_propagator for g in table_gates]))
+    tau = np.array([g.tau for g in table_gates], dtype=np.float64)
+    offsets, index, _ = pack_sequences([slot_of[i] for i in indices])
+    basis = as_c128(np.asarray(plan['basis']))
+    single_qubit = int(d == 2 and getattr(plan['basis'], 'btype', None) in ('Pauli', 'GGM'))
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    n_idx = len(idx)
+    shape = (N, N) if stage == 'error_transfer_matrix' else (n_idx, N, N)
+    out = np.empty((K, P) + shape, dtype=np.float64)
+    flags = np.zeros((K, P), dtype=np.int32)
+    total = np.empty((P, d, d), dtype=np.complex128) if want_U else None
+    check(_lib.load().ffk_sequence_processes(
+        handles, slots.ctypes.data, None if table is None else table.ctypes.data, U.ctypes.data, tau.ctypes.data,
+        len(table_gates), offsets.ctypes.data, index.ctypes.data, P, omega.ctypes.data, W, basis.ctypes.data, 1, d, A,
+        N, single_qubit, S.ctypes.data, S.ndim - 1, K, idx.ctypes.data, n_idx, _STAGES[stage], out.ctypes.data,
+        flags.ctypes.data, None if total is None else total.ctypes.data))
+    if stage == 'error_transfer_matrix':
+        bad = flags != 0
+    else:
+        bad = ~np.isfinite(out.reshape(K, P, -1)).all(axis=2)
+    return out, bad, total
+
+
+def _concatenated(gates, sequence, omega):
+    """The loop's pulse of one sequence."""
+    import filter_functions_amd as ff         # (the public names, as a caller's loop reads them)
+    table = np.empty(len(gates), dtype=object)
+    table[:] = gates
+    return ff.concatenate(table[sequence], omega=omega)
+
+
+def _loop(stage, gates, indices, spectra, omega, n_oper_identifiers, want_U):
+    """The loop's expression for every sequence under every spectrum: (values (K, P, ...), total propagators)."""
+    pulses = [_concatenated(gates, i, omega) for i in indices]
+    out = np.stack([np.stack([_single(stage, pulse, S, omega, n_oper_identifiers) for pulse in pulses])
+                    for S in spectra])
+    return out, np.stack([np.array(pulse.total_propagator) for pulse in pulses]) if want_U else None
+
+
+def _results(stage, gates, sequences, spectrum, omega, n_oper_identifiers, stacked, return_propagators):
+    from .pulse_sequence import PulseSequence
+    gates = list(gates)
+    for gate in gates:
+        if not isinstance(gate, PulseSequence):
+            raise TypeError('Can only concatenate PulseSequences!')
+    indices = index_arrays(sequences, len(gates))
+    if not indices:
+        raise ValueError('Need at least one sequence.')
+    spectra = stacked_spectra(spectrum, stacked)
+    want_U = bool(return_propagators)
+
+    def answer(values, total):
+        values = values if stacked else values[0]
+        return (values, total) if want_U else values
+    # routing, once per call: the gate set, then the spectra
+    plan = eligibility(gates) if all(S.ndim in (1, 2) for S in spectra) and len(omega) >= 2 else None
+    if plan is not None:
+        missing = [g for g in gates if not _on_grid(g, omega)]
+        if missing:
+            from .batch import get_filter_functions
+            get_filter_functions(missing, omega)
+        if not all('total_propagator' in g._data for g in gates):
+            plan = None
+    S = None
+    if plan is not None:
+        omega = as_f64(omega)
+        idx = np.asarray(util.get_indices_from_identifiers(gates[0].n_oper_identifiers, n_oper_identifiers))
+        S = _real_weights([util.parse_spectrum(one, omega, idx) for one in spectra]) if len(idx) else None
+    if S is None:
+        return answer(*_loop(stage, gates, indices, spectra, omega, n_oper_identifiers, want_U))
+    d, N, A, W, P, K, n_idx = plan['d'], plan['N'], plan['A'], len(omega), len(indices), len(S), len(idx)
+    single_qubit = d == 2 and getattr(plan['basis'], 'btype', None) in ('Pauli', 'GGM')
+    shape = (N, N) if stage == 'error_transfer_matrix' else (n_idx, N, N)
+    values = np.empty((K, P) + shape, dtype=np.float64)
+    bad = np.zeros((K, P), dtype=bool)
+    total = np.empty((P, d, d), dtype=np.complex128) if want_U else None
+    longest = max(len(i) for i in indices)
+    # (so many spectra that two sequences exceed the cumulant functions of one launch: several calls over the spectra)
+    k_step = K if _STAGES[stage] == 1 or single_qubit else max(1, min(K, MAX_CUMULANTS//(2*n_idx)))
+    for k0 in range(0, K, k_step):
+        part_S = np.ascontiguousarray(S[k0:k0 + k_step])
+        per_sequence = pass_bytes(longest, d, A, W, n_idx, len(part_S))
+        budget = max(PASS_BYTES - table_bytes(len(gates), d, A, W, n_idx, len(part_S), S.ndim - 1), 2*per_sequence)
+        for chunk in split_passes(list(range(P)), per_sequence, budget,
+                                  max_sequences(n_idx, len(part_S), stage, single_qubit)):
+            got, flags, U = _run_pass(gates, [indices[i] for i in chunk], plan, omega, part_S, idx, stage,
+                                      want_U and k0 == 0)
+            values[k0:k0 + k_step, chunk[0]:chunk[-1] + 1] = got
+            bad[k0:k0 + k_step, chunk[0]:chunk[-1] + 1] = flags
+            if U is not None:
+                total[chunk[0]:chunk[-1] + 1] = U
+    # the members whose result is not finite: what the loop does
+    if bad.any():
+        for i in np.flatnonzero(bad.any(axis=0)):
+            pulse = _concatenated(gates, indices[i], omega)
+            for k in np.flatnonzero(bad[:, i]):
+                values[k, i] = _single(stage, pulse, spectra[k], omega, n_oper_identifiers)
+    return answer(values, total)
+
+
+_SHARED = r"""
+
+    *gates* is a sequence of T ``PulseSequence`` objects, *sequences* a list of P one-dimensional integer arrays of
+    indices into it, read as :func:`ff.sequence_infidelities <filter_functions_amd.sequence_infidelities.
+    sequence_infidelities>` reads them (negative indices wrap, others out of range raise IndexError, an empty sequence
+    ValueError, an index that is no integer TypeError).  Values and exceptions are the loop's.  With *stacked* the
+    spectrum carries a leading axis of K spectra -- (K, n_omega), (K, n_idx, n_omega) or (K, n_idx, n_idx, n_omega);
+    K = 0 raises ValueError -- and the result a leading axis K: ``np.stack`` of the calls with ``spectrum[k]``, each
+    parsed in order.  With *return_propagators* the total propagators (P, d, d) are returned as well.
+
+    Routing, once per call.  The batched route is taken by the gate sets :func:`ff.sequence_infidelities` takes (all
+    gates d = 2 or all d = 4, one Hermitian traceless basis of d^2 elements, the same one to four noise operators,
+    total propagators known) under spectra of one or two dimensions without imaginary part, on at least two
+    frequencies, with at least one operator selected.  Gates without a control matrix on the grid are completed first
+    by one ``ff.get_filter_functions`` call; otherwise no ``PulseSequence`` is created and no gate's cache is touched;
+    resident gates are read in place.  A pass is one H2D copy, a fixed number of launches whatever P and K, and one
+    D2H copy; the decay amplitudes are formed from the registers of the concatenation rule, the sequences' control
+    matrices are never written, and the K spectra cost one walk of the sequences.  A sequence's result is the same
+    bits alone or among others, in any pass split, stacked or one spectrum at a time.  Everything else --
+    cross-spectra, other dimensions, ineligible gate sets -- and every sequence whose result is not finite evaluates
+    the loop's expression inside the call.  Second order and pulse correlations are not offered."""
+
+
+def sequence_decay_amplitudes(gates, sequences, spectrum, omega, n_oper_identifiers=None, stacked=False,
+                              return_propagators=False):
+    r"""Decay amplitudes :math:`\Gamma_{\alpha\beta,kl}` of many sequences of gates drawn from one gate set:
+
+    ``np.stack([numeric.calculate_decay_amplitudes(ff.concatenate(np.asarray(gates, dtype=object)[s], omega=omega),
+    spectrum, omega, n_oper_identifiers) for s in sequences])``
+
+    of shape (P, n_idx, N, N), or (P, n_idx, n_idx, N, N) for a cross-spectrum."""
+    return _results('decay_amplitudes', gates, sequences, spectrum, omega, n_oper_identifiers, stacked,
+                    return_propagators)
+
+
+def sequence_cumulant_functions(gates, sequences, spectrum, omega, n_oper_identifiers=None, stacked=False,
+                                return_propagators=False):
+    r"""Cumulant functions :math:`\mathcal{K}_{\alpha\beta}` of many sequences of gates drawn from one gate set, the
+    shape of :func:`sequence_decay_amplitudes`:
+
+    ``np.stack([numeric.calculate_cumulant_function(ff.concatenate(np.asarray(gates, dtype=object)[s], omega=omega),
+    spectrum, omega, n_oper_identifiers) for s in sequences])``."""
+    return _results('cumulant_function', gates, sequences, spectrum, omega, n_oper_identifiers, stacked,
+                    return_propagators)
+
+
+def sequence_error_transfer_matrices(gates, sequences, spectrum, omega, n_oper_identifiers=None, stacked=False,
+                                     return_propagators=False):
+    r"""Error transfer matrices :math:`\exp\mathcal{K}` of many sequences of gates drawn from one gate set, shape
+    (P, N, N):
+
+    ``np.stack([ff.error_transfer_matrix(ff.concatenate(np.asarray(gates, dtype=object)[s], omega=omega), spectrum,
+    omega, n_oper_identifiers) for s in sequences])``."""
+    return _results('error_transfer_matrix', gates, sequences, spectrum, omega, n_oper_identifiers, stacked,
+                    return_propagators)
+
+
+for _function in (sequence_decay_amplitudes, sequence_cumulant_functions, sequence_error_transfer_matrices):
+    _function.__doc__ += _SHARED
+del _function

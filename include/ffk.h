@@ -752,6 +752,34 @@ int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slo
                                  double* decay_amplitudes, double* cumulant_function, double* error_transfer_matrix,
                                  int32_t* not_finite);
 
+/* ---- decay amplitudes, cumulant functions and error transfer matrices of many gate sequences from one gate set in
+ *      ONE pass, under any number of spectra (ff.sequence_decay_amplitudes, ff.sequence_cumulant_functions,
+ *      ff.sequence_error_transfer_matrices) ----
+ * Sequences, gates, slots, gate_table, gate_propagators, tau, omega, basis and idx as for ffk_sequence_infidelities
+ * (Hermitian basis; (d, N) = (2, 4) or (4, 16), 1 <= A <= 4; W >= 2).  spectrum (n_spectra, W) for s_ndim = 1 or
+ * (n_spectra, n_idx, W) for s_ndim = 2, f64 host: real weights only, cross-spectra are not taken.  stage selects what
+ * `out` receives: 1 the decay amplitudes (n_spectra, P, n_idx, N, N) f64, 2 the cumulant functions of the same shape
+ * (single_qubit as for ffk_cumulant_function), 3 the error transfer matrices (n_spectra, P, N, N), the exponential of
+ * the cumulant function summed over the selected operators.  not_finite (n_spectra, P) int32: at stage 3, 1 where
+ * that sum holds a NaN or Inf (the matrix is then not written); 0 at the other stages.  total_propagators (P, d, d)
+ * c128 host may be NULL.  The decay amplitudes are formed from the registers of the concatenation rule at the end of
+ * each sequence: the sequences' control matrices are never written to memory, and every spectrum beyond the first
+ * costs one more epilogue, not one more walk.  One H2D copy, a fixed number of launches whatever P and n_spectra --
+ * the front, the weights, the rule with Gamma, the sum of the frequency blocks' partial tiles in block order, then
+ * the cumulant functions and the exponentials as ffk_resident_batch_processes runs them --, one D2H copy.  Arena
+ * workspace, no result handle.  Gamma of one operator is symmetric bit for bit, and a sequence's result is the same
+ * bits whatever else is in the pass, whatever its place and however many spectra the call carries.  At stage 2 and 3
+ * without single_qubit n_spectra * P * n_idx <= 65535.  Bad arguments: FFK_EINVAL before anything touches the
+ * device.  The workspace query needs no GPU (0: unsupported shape). */
+size_t ffk_sequence_processes_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                              int n_idx, int s_ndim, int n_spectra, int stage);
+int ffk_sequence_processes(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                           const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                           const int32_t* index, int P, const double* omega, int W, const double* basis,
+                           int hermitian_basis, int d, int A, int N, int single_qubit, const double* spectrum,
+                           int s_ndim, int n_spectra, const int32_t* idx, int n_idx, int stage, double* out,
+                           int32_t* not_finite, double* total_propagators);
+
 /* ---- one-sided all-gather of the F blocks over xGMI (frequency-sharded step; the
  *      reference has no multi-device path: numeric.py:846-869 is embarrassingly parallel in omega
  *      and this is the exchange that reassembles F(omega) for util.integrate, util.py:880-906) ----

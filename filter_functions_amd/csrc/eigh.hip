@@ -5,7 +5,7 @@
 // accumulator live in LDS; the D/2 disjoint rotations of one round-robin step of the cyclic
 // Jacobi method are computed and applied by the 64 lanes in parallel (complex Hermitian
 // rotations, rows then columns).  Only the lower triangle of the input is read, like
-// LAPACK's UPLO='L' default; eigenvalues are returned ascending.
+// LAPACK's UPLO='L' default; eigenvalues are returned ascending, eigenvectors normalised.
 #include <algorithm>
 
 #include "ffk_internal.h"
@@ -59,9 +59,17 @@ __device__ __forceinline__ bool jacobi_rotation(cplx apq, double alpha, double* 
     return true;
 }
 
+// The squares |a_pq|^2 that the rotations and the convergence test are built on neither underflow
+// nor overflow while the squared Frobenius norm lies in this range: entries of (eps ||A||_F)^2 are
+// still normal numbers at the lower end, alpha^2 + |a_pq|^2 <= ||A||_F^2 stays below the rotation
+// guard at the upper.  Outside it (||A||_F < 1e-135 or >= 1e150, Inf entries) "nothing to rotate"
+// and "off <= tol2*tot" would hold for matrices that are far from diagonal: only the exact zero
+// matrix is accepted there, every other segment is flagged.
+constexpr double kNorm2Min = 1e-270, kNorm2Max = 1e300;
+
 // One wavefront: eigendecomposition of Hg (lower triangle), eigenvalues/eigenvectors to global
 // memory in ascending order, segment propagator P = V exp(-i D dt) V^dag to `P` (LDS or global).
-// Returns false if the Jacobi iteration clearly failed to converge.
+// Returns false if the Jacobi iteration clearly failed to converge or the matrix is out of range.
 template <int D>
 __device__ __forceinline__ bool eigh_expm_wave(EighState<D>& st, const cplx* __restrict__ Hg, double dtg, int lane,
                                double* __restrict__ eigvals_g, cplx* __restrict__ eigvecs_g,
@@ -89,7 +97,7 @@ __device__ __forceinline__ bool eigh_expm_wave(EighState<D>& st, const cplx* __r
     wave_sync();
 
     const double tol2 = static_cast<double>(D*D)*4.930380657631324e-32;  // (D eps)^2
-    bool converged = false;
+    bool converged = false, in_range = true;
     // A dense matrix needs at least four sweeps to reach (D eps)^2: the convergence test (an LDS
     // pass and two wave reductions) starts after the third; on an already diagonal matrix the
     // untested sweeps are no-ops (nothing to rotate).
@@ -108,6 +116,7 @@ __device__ __forceinline__ bool eigh_expm_wave(EighState<D>& st, const cplx* __r
             tot = wave_sum(tot);
             if (off <= tol2*tot) {
                 converged = true;
+                in_range = tot >= kNorm2Min && tot < kNorm2Max;   // (tot is in a register already)
                 break;
             }
         }
@@ -246,8 +255,43 @@ __device__ __forceinline__ bool eigh_expm_wave(EighState<D>& st, const cplx* __r
         off = wave_sum(off);
         tot = wave_sum(tot);
         ok = off <= 1e-24*tot;
+        in_range = tot >= kNorm2Min && tot < kNorm2Max;
+    }
+    if (!in_range) {
+        // never taken on data in range: is this the zero matrix (an idle segment) or one whose squares
+        // underflowed, overflowed or are not finite?
+        bool nonzero = false;
+        for (int e = lane; e < D*D; e += 64) {
+            const cplx a = A[e / D][e % D];
+            nonzero |= !(a.re == 0.0 && a.im == 0.0);
+        }
+        if (__any(nonzero)) ok = false;
     }
 
+    // Unit eigenvectors.  A rotation by an angle so small that its cosine rounds to 1 stretches its two
+    // columns by 1 + |w|^2/2, never shrinks them: over the sweeps t = |v_i|^2 - 1 grows to ~1e-15 (d = 16)
+    // with one sign, the propagators V e^{-i D dt} V^dag are too long by as much, and their product
+    // drifts linearly in the number of segments.  The tracked diagonal is v_i^dag H v_i of the
+    // unnormalised vector: the eigenvalue is the Rayleigh quotient, a_ii/|v_i|^2.  The columns are
+    // corrected by v += e v with e = (1 + t)^(-1/2) - 1 = -t/2 + 3t^2/8 (|t| << 1e-5 after unitary
+    // rotations; a factor 1 + e itself would be quantised to the ulp of 1, with a bias of its own) on
+    // their way to global memory; the columns in LDS stay as they are and the phase factor carries
+    // their (1 + e)^2 into the propagator.
+    double ce = 0.0, cf = 0.0;      // e and (1 + e)^2 - 1 of this lane's column
+    if (lane < D) {
+        double tr = -1.0, ti = 0.0;
+        for (int row = 0; row < D; ++row) {
+            const cplx v = V[row][lane];
+            tr = fma(v.re, v.re, tr);
+            ti = fma(v.im, v.im, ti);
+        }
+        const double t = tr + ti;
+        ce = t*fma(0.375, t, -0.5);
+        cf = ce*(2.0 + ce);
+        const double li = A[lane][lane].re;
+        A[lane][lane].re = fma(cf, li, li);
+    }
+    wave_sync();
     // ascending order by rank (stable), write eigenvalues / eigenvectors
     if (lane < D) {
         const double li = A[lane][lane].re;
@@ -257,9 +301,13 @@ __device__ __forceinline__ bool eigh_expm_wave(EighState<D>& st, const cplx* __r
             rank += (lj < li || (lj == li && j < lane)) ? 1 : 0;
         }
         eigvals_g[rank] = li;
-        for (int row = 0; row < D; ++row) eigvecs_g[row*D + rank] = V[row][lane];
+        for (int row = 0; row < D; ++row) {
+            const cplx v = V[row][lane];
+            eigvecs_g[row*D + rank] = {fma(ce, v.re, v.re), fma(ce, v.im, v.im)};
+        }
         // exp(-i lambda dt): argument rounded exactly like util.cexp(-dt*eigvals), numeric.py:1929
-        st.phase[lane] = cexp(-(dtg*li));
+        const cplx ph = cexp(-(dtg*li));
+        st.phase[lane] = {fma(cf, ph.re, ph.re), fma(cf, ph.im, ph.im)};
     }
     wave_sync();
     // P = V diag(phase) V^dag  (column pairing is order independent)

@@ -141,7 +141,9 @@ __global__ __launch_bounds__(kGenThreads) void eigh_expm_generic_kernel(
         *off = block_sum(o, red);
         *tot = block_sum(t, red);
     };
-    bool converged = false;
+    // the range of ||A||_F^2 in which no square underflows or overflows: see eigh.hip
+    constexpr double kNorm2Min = 1e-270, kNorm2Max = 1e300;
+    bool converged = false, in_range = true;
     constexpr int kMaxSweeps = 60;
     for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
         if (sweep >= 3) {
@@ -149,6 +151,7 @@ __global__ __launch_bounds__(kGenThreads) void eigh_expm_generic_kernel(
             off_and_total(&off, &tot);
             if (off <= tol2*tot) {
                 converged = true;
+                in_range = tot >= kNorm2Min && tot < kNorm2Max;
                 break;
             }
         }
@@ -220,7 +223,30 @@ __global__ __launch_bounds__(kGenThreads) void eigh_expm_generic_kernel(
         double off, tot;
         off_and_total(&off, &tot);
         ok = off <= 1e-24*tot;
+        in_range = tot >= kNorm2Min && tot < kNorm2Max;
     }
+    if (!in_range) {      // (block-uniform) only the exact zero matrix is accepted out of range
+        int nonzero = 0;
+        for (int e = tid; e < dd; e += kGenThreads) nonzero |= !(A[e].re == 0.0 && A[e].im == 0.0);
+        if (__syncthreads_or(nonzero)) ok = false;
+    }
+    // unit eigenvectors, eigenvalues as Rayleigh quotients a_ii/|v_i|^2 (see eigh.hip: the columns only grow);
+    // t = |v_i|^2 - 1, e = (1 + t)^(-1/2) - 1
+    if (tid < d) {
+        double t = -1.0;
+        for (int row = 0; row < d; ++row) {
+            const cplx v = V[row*d + tid];
+            t = fma(v.re, v.re, fma(v.im, v.im, t));
+        }
+        const double e = t*fma(0.375, t, -0.5);
+        for (int row = 0; row < d; ++row) {
+            const cplx v = V[row*d + tid];
+            V[row*d + tid] = {fma(e, v.re, v.re), fma(e, v.im, v.im)};
+        }
+        const double li = A[tid*d + tid].re;
+        A[tid*d + tid].re = fma(e*(2.0 + e), li, li);
+    }
+    __syncthreads();
     // ascending order by rank (stable), eigenvalues / eigenvectors out
     double* ev = eigvals + static_cast<size_t>(g)*d;
     cplx* vg = eigvecs + static_cast<size_t>(g)*dd;

@@ -68,6 +68,10 @@ def diagonalize(hamiltonian, dt):
     eigvals (n_dt, d) ascending; eigvecs (n_dt, d, d), eigenvectors in columns (defined up to
     the usual phase / degenerate-subspace gauge); propagators (n_dt+1, d, d) with
     ``propagators[0] = 1`` and ``propagators[g+1] = V_g exp(-i D_g dt_g) V_g^dag propagators[g]``.
+
+    Raises ``numpy.linalg.LinAlgError`` for a segment that does not converge (NaN entries), has an
+    infinite entry, or whose Frobenius norm is below 1e-135 or above 1e150 without being exactly
+    zero: the squares the Jacobi iteration is built on underflow or overflow there.
     """
     H = as_c128(hamiltonian)
     dt = as_f64(dt)

@@ -24,6 +24,7 @@ from .gradient import infidelity_derivative
 from .numeric import error_transfer_matrix, infidelity
 from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
 from .sequences import concatenate_sequences
+from .sequence_correlations import sequence_correlation_infidelities
 from .sequence_infidelities import sequence_infidelities
 from .sequence_processes import (sequence_cumulant_functions, sequence_decay_amplitudes,
                                  sequence_error_transfer_matrices)
@@ -40,7 +41,8 @@ __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradie
            'error_transfer_matrices', 'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
            'filter_function_derivatives', 'frequency_shifts', 'infidelity_derivative', 'infidelity_derivatives',
            'liouville_representation', 'numeric', 'processes',
-           'pulse_sequence', 'remap', 'sequence_cumulant_functions', 'sequence_decay_amplitudes',
+           'pulse_sequence', 'remap', 'sequence_correlation_infidelities', 'sequence_correlations',
+           'sequence_cumulant_functions', 'sequence_decay_amplitudes',
            'sequence_error_transfer_matrices', 'sequence_infidelities', 'sequence_processes', 'sequences',
            'superoperator', 'util']
 

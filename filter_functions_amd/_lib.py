@@ -264,6 +264,12 @@ SIGNATURES = {
                                                       c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                                       c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                                       c_int, c_void_p, c_void_p]),
+    'ffk_sequence_correlation_infidelities4_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int,
+                                                                          c_int, c_int, c_int, c_int]),
+    'ffk_sequence_correlation_infidelities4': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                       c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                                       c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                                       c_int, c_void_p, c_void_p]),
     'ffk_sequence_infidelities_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                              c_int, c_int]),
     'ffk_sequence_infidelities': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,

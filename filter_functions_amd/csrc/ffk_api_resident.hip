@@ -1131,32 +1131,37 @@ CorrLayout corr_layout(int T, int P, size_t n_index, int n_host, int d, int A, i
     return L;
 }
 
-bool corr_shape_ok(int T, int P, int d, int A, int N, int W, int n_idx, int s_ndim) {
-    return T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && ffk::sequences_supported(d, N, A) && W >= 1 &&
+bool corr_shape_ok(bool two_qubit, int T, int P, int d, int A, int N, int W, int n_idx, int s_ndim) {
+    return T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) &&
+           (two_qubit ? ffk::sequences4_supported(d, N, A) : ffk::sequences_supported(d, N, A)) && W >= 1 &&
            (s_ndim == 1 || s_ndim == 2) && n_idx >= 1 && n_idx <= A;
 }
 
-}  // namespace
-
-size_t ffk_sequence_correlation_infidelities_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A,
-                                                             int N, int W, int n_idx, int s_ndim) {
-    if (!corr_shape_ok(T, P, d, A, N, W, n_idx, s_ndim) || n_index < P || n_host < 0 || n_host > T) return 0;
+size_t corr_workspace_bytes(bool two_qubit, int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                            int n_idx, int s_ndim) {
+    if (!corr_shape_ok(two_qubit, T, P, d, A, N, W, n_idx, s_ndim) || n_index < P || n_host < 0 || n_host > T) return 0;
     // the lengths are not known here: no sequence is longer than the cap or than all positions together
     const size_t longest = std::min(size_t(ffk::correlation_max_length()), size_t(n_index));
     return corr_layout(T, P, size_t(n_index), n_host, d, A, N, W, spectrum_shape(s_ndim, n_idx), n_idx,
                        size_t(n_index)*longest).end;
 }
 
-int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
-                                          const double* gate_propagators, const double* tau, int T,
-                                          const int32_t* offsets, const int32_t* index, int P, const double* omega,
-                                          int W, const double* basis, int hermitian_basis, int d, int A, int N,
-                                          const double* spectrum, int s_ndim, int spectrum_is_real, const int32_t* idx,
-                                          int n_idx, int d_infidelity, const int64_t* out_offsets, double* infidelity) {
+// The pass of both entries: single-qubit gates on the kernels of correlations.hip, two-qubit gates (two_qubit) on
+// those of correlations_d4.hip behind the front launch of their dimension.
+int correlation_pass(bool two_qubit, ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                     const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                     const int32_t* index, int P, const double* omega, int W, const double* basis,
+                     int hermitian_basis, int d, int A, int N, const double* spectrum, int s_ndim,
+                     int spectrum_is_real, const int32_t* idx, int n_idx, int d_infidelity,
+                     const int64_t* out_offsets, double* infidelity) {
     FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis && spectrum && idx &&
                 out_offsets && infidelity, "NULL argument");
-    FFK_REQUIRE(ffk::sequences_supported(d, N, A), "unsupported shape d=%d N=%d A=%d (need d = 2, N = 4, 1 <= A <= 4)",
-                d, N, A);
+    if (two_qubit)
+        FFK_REQUIRE(ffk::sequences4_supported(d, N, A),
+                    "unsupported shape d=%d N=%d A=%d (need d = 4, N = 16, 1 <= A <= 4)", d, N, A);
+    else
+        FFK_REQUIRE(ffk::sequences_supported(d, N, A), "unsupported shape d=%d N=%d A=%d (need d = 2, N = 4, 1 <= A <= 4)",
+                    d, N, A);
     FFK_REQUIRE(hermitian_basis != 0, "the batched pass needs a Hermitian basis");
     FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
     FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 1,
@@ -1230,16 +1235,28 @@ int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int3
     double* dQc = reinterpret_cast<double*>(at(L.Qc));
     cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
     double* dPart = reinterpret_cast<double*>(at(L.part));
-    FFK_HIP(ffk::launch_sequences_front(reinterpret_cast<const cplx*>(at(L.U)), reinterpret_cast<const double*>(at(L.tau)),
-                                        dOmega, T, W, dOff, dIdx, P, reinterpret_cast<const cplx*>(at(L.basis)), dPh,
-                                        dL, reinterpret_cast<cplx*>(at(L.Q)), s));
-    FFK_HIP(ffk::launch_correlation_prefix(dL, dOff, dIdx, P, dQc, s));
+    const cplx* dU = reinterpret_cast<const cplx*>(at(L.U));
+    const double* dTau = reinterpret_cast<const double*>(at(L.tau));
+    const cplx* dBasis = reinterpret_cast<const cplx*>(at(L.basis));
+    const cplx* const* dTab = reinterpret_cast<const cplx* const*>(at(L.tab));
+    const int32_t* dMembers = reinterpret_cast<const int32_t*>(at(L.members));
+    const int32_t* dSel = reinterpret_cast<const int32_t*>(at(L.idx));
+    cplx* dQ = reinterpret_cast<cplx*>(at(L.Q));
+    if (two_qubit) {
+        FFK_HIP(ffk::launch_sequences4_front(dU, dTau, dOmega, T, W, dOff, dIdx, P, dBasis, dPh, dL, dQ, s));
+        FFK_HIP(ffk::launch_correlations4_prefix(dL, dOff, dIdx, P, dQc, s));
+    } else {
+        FFK_HIP(ffk::launch_sequences_front(dU, dTau, dOmega, T, W, dOff, dIdx, P, dBasis, dPh, dL, dQ, s));
+        FFK_HIP(ffk::launch_correlation_prefix(dL, dOff, dIdx, P, dQc, s));
+    }
     FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(sh.rows), W, dOmega, W, 0, dScale,
                                          s));
-    FFK_HIP(ffk::launch_correlation_gram(dPh, reinterpret_cast<const cplx* const*>(at(L.tab)), dQc, dOff, dIdx, dOut,
-                                         reinterpret_cast<const int32_t*>(at(L.members)), class_counts, W, dScale,
-                                         s_ndim, reinterpret_cast<const int32_t*>(at(L.idx)), n_idx, d_infidelity,
-                                         int64_t(total), dPart, s));
+    if (two_qubit)
+        FFK_HIP(ffk::launch_correlations4_gram(dPh, dTab, dQc, dOff, dIdx, dOut, dMembers, class_counts, W, dScale,
+                                               s_ndim, dSel, n_idx, d_infidelity, int64_t(total), dPart, s));
+    else
+        FFK_HIP(ffk::launch_correlation_gram(dPh, dTab, dQc, dOff, dIdx, dOut, dMembers, class_counts, W, dScale,
+                                             s_ndim, dSel, n_idx, d_infidelity, int64_t(total), dPart, s));
     FFK_HIP(ffk::launch_correlation_reduce(dPart, dOut, dOff, P, n_idx, W, int64_t(total),
                                            reinterpret_cast<double*>(at(L.infid)), s));
     FFK_HIP(hipMemcpyAsync(hp + L.infid, dp + L.infid, 8*total*n_idx, hipMemcpyDeviceToHost, s));
@@ -1247,6 +1264,42 @@ int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int3
     if (int rc = kernel_fault_status()) return rc;
     std::memcpy(infidelity, hp + L.infid, 8*total*n_idx);
     return FFK_OK;
+}
+
+}  // namespace
+
+size_t ffk_sequence_correlation_infidelities_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A,
+                                                             int N, int W, int n_idx, int s_ndim) {
+    return corr_workspace_bytes(false, T, P, n_index, n_host, d, A, N, W, n_idx, s_ndim);
+}
+
+int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                          const double* gate_propagators, const double* tau, int T,
+                                          const int32_t* offsets, const int32_t* index, int P, const double* omega,
+                                          int W, const double* basis, int hermitian_basis, int d, int A, int N,
+                                          const double* spectrum, int s_ndim, int spectrum_is_real, const int32_t* idx,
+                                          int n_idx, int d_infidelity, const int64_t* out_offsets, double* infidelity) {
+    return correlation_pass(false, gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                            hermitian_basis, d, A, N, spectrum, s_ndim, spectrum_is_real, idx, n_idx, d_infidelity,
+                            out_offsets, infidelity);
+}
+
+// ---- the same for two-qubit gates, (d, N) = (4, 16) (ff.sequence_correlation_infidelities; correlations_d4.hip) ----
+size_t ffk_sequence_correlation_infidelities4_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A,
+                                                              int N, int W, int n_idx, int s_ndim) {
+    return corr_workspace_bytes(true, T, P, n_index, n_host, d, A, N, W, n_idx, s_ndim);
+}
+
+int ffk_sequence_correlation_infidelities4(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                           const double* gate_propagators, const double* tau, int T,
+                                           const int32_t* offsets, const int32_t* index, int P, const double* omega,
+                                           int W, const double* basis, int hermitian_basis, int d, int A, int N,
+                                           const double* spectrum, int s_ndim, int spectrum_is_real, const int32_t* idx,
+                                           int n_idx, int d_infidelity, const int64_t* out_offsets,
+                                           double* infidelity) {
+    return correlation_pass(true, gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                            hermitian_basis, d, A, N, spectrum, s_ndim, spectrum_is_real, idx, n_idx, d_infidelity,
+                            out_offsets, infidelity);
 }
 
 // ---- infidelities of many sequences from one gate table in ONE pass, single- or two-qubit gates

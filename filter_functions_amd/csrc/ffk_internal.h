@@ -424,6 +424,18 @@ hipError_t launch_correlation_gram(const cplx* phases, const cplx* const* Rtab, 
 hipError_t launch_correlation_reduce(const double* part, const int64_t* out_offsets, const int32_t* offsets, int P,
                                      int n_idx, int W, int64_t total, double* out, hipStream_t stream);
 
+// ---- correlations_d4.hip ----------------------------------------------------------------------
+// The same pass for two-qubit gates (d = 4, N = 16, A <= 4), after launch_sequences4_front: Qc (n_index, 16, 16),
+// one block per sequence; the Gram launches take the arguments, classes and slabs of launch_correlation_gram and are
+// followed by launch_correlation_reduce.
+hipError_t launch_correlations4_prefix(const double* Lpulse, const int32_t* offsets, const int32_t* index, int P,
+                                       double* Qc, hipStream_t stream);
+hipError_t launch_correlations4_gram(const cplx* phases, const cplx* const* Rtab, const double* Qc,
+                                     const int32_t* offsets, const int32_t* index, const int64_t* out_offsets,
+                                     const int32_t* members, const int* class_counts, int W, const cplx* scale,
+                                     int s_ndim, const int32_t* idx, int n_idx, int d, int64_t total, double* part,
+                                     hipStream_t stream);
+
 // ---- decay.hip -------------------------------------------------------------------------------
 // Gamma (Gp,Gp,n_idx[,n_idx],N,N) f64 from R (Gp,A,N,W) c128 (Gp = 1: the total control matrix),
 // S c128 (W,), (n_idx,W) or (n_idx,n_idx,W); omega (Wg,) is the global grid of which R and S hold

@@ -705,6 +705,28 @@ int ffk_sequence_correlation_infidelities(ffk_resident* const* gates, const int3
                                           const double* spectrum, int s_ndim, int spectrum_is_real, const int32_t* idx,
                                           int n_idx, int d_infidelity, const int64_t* out_offsets, double* infidelity);
 
+/* ---- the same for two-qubit gates (ff.sequence_correlation_infidelities) ----
+ * ffk_sequence_correlation_infidelities for (d, N) = (4, 16), 1 <= A <= 4, Hermitian basis: the same arguments and
+ * conventions -- CSR offsets / index, every sequence 1 ... 256 positions, out_offsets the prefix sums of G_p^2, the
+ * ragged (out_offsets[P], n_idx) output, spectra of one or two dimensions without an imaginary part, W >= 2 --, arena
+ * workspace, one H2D copy, one D2H copy, no result handle, five to eight launches whatever P: phases, Liouville
+ * representations (T, 16, 16) and total propagators; the propagator accumulated before every position, (n_index, 16,
+ * 16) f64, one block per sequence; the spectral weights; one Gram launch per class of lengths that has members (up
+ * to 32, 64, 128, 256 positions); the slab reduction.  A Gram block generates the summands of 8, 4, 2 or 1
+ * frequencies in LDS with vector FMAs and accumulates the real Gram matrix of the positions on the FP64 matrix
+ * cores, eight K-steps per tile pair and frequency.  A sequence's result is the same bits whatever else is in the
+ * pass, and exactly symmetric.  Any other (d, N), the single-qubit shape included, is FFK_EINVAL here and 0 from the
+ * workspace query, which needs no GPU.  Bad arguments: FFK_EINVAL before anything touches the device. */
+size_t ffk_sequence_correlation_infidelities4_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A,
+                                                              int N, int W, int n_idx, int s_ndim);
+int ffk_sequence_correlation_infidelities4(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                           const double* gate_propagators, const double* tau, int T,
+                                           const int32_t* offsets, const int32_t* index, int P, const double* omega,
+                                           int W, const double* basis, int hermitian_basis, int d, int A, int N,
+                                           const double* spectrum, int s_ndim, int spectrum_is_real, const int32_t* idx,
+                                           int n_idx, int d_infidelity, const int64_t* out_offsets,
+                                           double* infidelity);
+
 /* ---- infidelities of many gate sequences from one gate set in ONE pass (ff.sequence_infidelities) ----
  * infidelity (P, n_idx) f64 host, or (P, n_idx, n_idx) for s_ndim = 3: what ffk_concatenate_sequences_resident
  * returns as `infidelity`, without a result handle and without the sequences' control matrices, which this entry

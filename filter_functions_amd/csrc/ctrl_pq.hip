@@ -39,6 +39,10 @@
 //     ffk_control_matrix_dev / ffk_pipeline_dev), else the producers fold it per tile.  Round 7: with PRE, W_a and
 //     T go from global memory into the slot by LDS-DMA, and the consumer loop issues all its LDS operations in
 //     the gaps behind its matrix instructions (profiles/r07_*).
+//   * Round 8: the diagonal entries (dE = 0) are near a resonance, |w| < 2^-4/dt, for every frequency of a grid's lower
+//     decades and every segment.  They have a path of their own in the producers (the lane's reciprocal, one compare,
+//     a wavefront of near lanes only forms the polynomial value); the off-diagonal entries leave one scalar mask each;
+//     the threshold comes with the table row (DESIGN.md section 6.1 "Round 8", profiles/r08_*).
 //   * Flags in LDS: ready[slot] written by the slot's producer, done[slot] counted up by the consumers with
 //     ds_add, progress[consumer]; the lagging consumer of a SIMD raises its priority (the arbiter serves the
 //     oldest wavefront first and would let one run ahead until the ring stops it: soft lockstep).  Every wait is
@@ -146,9 +150,6 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
         __builtin_amdgcn_s_setprio(0);
         const int iw = blockIdx.x*64 + lane;
         double om = omega[iw < W ? iw : W - 1];
-        // (landed here, once: the loop's own counted waits below do not cover it, and hipcc would otherwise drain every
-        // load in flight, the next row's included, in front of its first use inside the loop)
-        asm volatile("" : "+v"(om));
         const int n_ops = (1 + n_alpha)*DD;            // <= 64: one staged element per lane
         double* row = rows + wave*S;
         struct Staged {
@@ -188,8 +189,15 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
                 asm volatile("" ::: "memory");
             }
         };
+        // the frequency and the first row are requested together
         Staged cur = {};
         if (wave < n_it) cur = request(wave);
+        // (the frequency has landed here, once: the loop's own counted waits below do not cover it, and hipcc would
+        // otherwise drain every load in flight, the next row's included, in front of its first use inside the loop)
+        asm volatile("" : "+v"(om));
+        // The diagonal entries have dE = 0: x = om + 0.0 and its reciprocal belong to the lane, not to the tile.
+        double r0 = rcp_fast(om + 0.0);
+        asm volatile("" : "+v"(r0));                   // (kept in its two registers, not formed again per tile)
         for (int it = wave; it < n_it; it += kPqProducers) {
             const int slot = it & (kPqRing - 1);
             const int gen = it/kPqRing;
@@ -215,14 +223,17 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
             // fetches them in pairs with a full LDS round trip between the pairs; all 13 at once take 104 registers).
             const double* st = row;
             const double2_t sbcb = *reinterpret_cast<const double2_t*>(st + seg_rec(lane >> 2) + 1);
-            const double2_t head = *reinterpret_cast<const double2_t*>(st);          // dt_g, t_g
+            const double4_t head = *reinterpret_cast<const double4_t*>(st);          // dt_g, t_g, 2^-4/dt_g
             const double sb = sbcb.x, cb = sbcb.y;
             // the tile: q of the 13 distinct entries (all diagonal entries coincide), psi
             const double dtg = head.x;
+            // the near-resonance threshold comes with the row (prep.hip::prologue_segment; pf.thr is not used here)
+            const double thr = head.z;
             cplx ph;
             sincos_pi<false>(om*head.y, &ph.im, &ph.re);
+            const double ha = 0.5*(om*dtg);            // the diagonal's half-angle a: sincos_pi's argument and the near form's
             double sa, ca;
-            sincos_pi<false>(0.5*(om*dtg), &sa, &ca);
+            sincos_pi<false>(ha, &sa, &ca);
             const PhasedFrequency pf = phased_frequency(om, dtg, ph, sa, ca);
             double q[DD];
             auto batch = [&](int e0, int e1) __attribute__((always_inline)) {
@@ -233,22 +244,44 @@ __global__ __launch_bounds__((kPqProducers + kPqConsumers)*64, 3) void ctrl_accu
                     rec[e] = *reinterpret_cast<const double4_t*>(st + seg_rec(e));
                 }
                 asm volatile("" ::: "memory");
-                // near a resonance (|x| < thr, rare) the entry is redone under one branch; whether any of the
-                // batch's entries is, is ONE running minimum of |x| (a compare, a select and an or per entry
-                // were a twelfth of the producer's instructions)
-                double xmin = pf.thr;
+                // Near a resonance (|x| < thr) an entry is redone from the short sine polynomial (phased_q).  For the
+                // off-diagonal entries that happens around the level splittings only: one compare per entry,
+                // independent of one another (a running minimum of |x| is a serial chain on a latency-bound
+                // wavefront), leaves each entry's near lanes as a scalar mask, which the redo below enters with.
+                bool near[DD];
+                unsigned long long any = 0;
 #pragma unroll
-                for (int e = 0; e < DD; ++e) {
-                    if (e < e0 || e >= e1 || (e != 0 && e/D == e%D)) continue;
+                for (int e = 1; e < DD; ++e) {
+                    if (e < e0 || e >= e1 || e/D == e%D) continue;
                     const double x = om + rec[e].x;
                     q[e] = fma(pf.sa2, rec[e].z, pf.ca2*rec[e].y)*rcp_fast(x);
-                    asm("v_min_f64 %0, |%1|, %0" : "+v"(xmin) : "v"(x));
+                    rec[e].x = x;
+                    near[e] = fabs(x) < thr;
+                    any |= __builtin_amdgcn_ballot_w64(near[e]);
                 }
-                if (xmin < pf.thr) {
+                // The diagonal entries (dE = 0, x = om + 0.0) are near for EVERY frequency below 2^-4/dt_g: the lower
+                // decades of a logarithmic grid, for every segment (tools/count_near_resonance.py).  One compare; the
+                // reciprocal is the lane's (r0), the half-angle the tile's own; a wavefront whose lanes are all near
+                // does not form the addition theorem's value at all.
+                if (e0 == 0) {
+                    const bool near0 = fabs(om) < thr;
+                    const unsigned long long lanes0 = __builtin_amdgcn_ballot_w64(near0);
+                    auto q_near0 = [&]() __attribute__((always_inline)) {
+                        const double s = sin_small<true>(ha);
+                        return om == 0.0 ? dtg : 2.0*s*r0;
+                    };
+                    if (lanes0 == ~0ull) {
+                        q[0] = q_near0();
+                    } else {
+                        q[0] = fma(pf.sa2, rec[0].z, pf.ca2*rec[0].y)*r0;
+                        if (near0) q[0] = q_near0();     // (skipped by the wavefront where no lane is near)
+                    }
+                }
+                if (any != 0) {
 #pragma unroll
-                    for (int e = 0; e < DD; ++e) {
-                        if (e < e0 || e >= e1 || (e != 0 && e/D == e%D)) continue;
-                        if (fabs(om + rec[e].x) < pf.thr) q[e] = phased_q(pf, rec[e].x, rec[e].y, rec[e].z);
+                    for (int e = 1; e < DD; ++e) {
+                        if (e < e0 || e >= e1 || e/D == e%D) continue;
+                        if (near[e]) q[e] = phased_q_near(rec[e].x, dtg);   // (skipped where no lane is near)
                     }
                 }
             };

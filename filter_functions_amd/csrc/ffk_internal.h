@@ -16,7 +16,9 @@ constexpr int kMaxD = 16;          // compile-time-D kernels (registers / wave-p
 constexpr int kMaxDGeneric = 64;   // runtime-d kernels of generic.hip (FFK_MAX_D)
 constexpr int kWave = 64;
 
-// Per-segment uniform table row (doubles): [0] = dt_g, [1] = t_g, [2..3] pad, then one 4-double
+// Per-segment uniform table row (doubles): [0] = dt_g, [1] = t_g, [2] = 2^-4/dt_g (+inf for dt_g = 0: the
+// near-resonance threshold of ffk_math.h::phased_frequency, written by prep.hip::prologue_segment and read by
+// the d = 4 producers, ctrl_pq.hip; the other kernels form it themselves), [3] pad, then one 4-double
 // record per matrix entry e = m*d + n:  (dE = D_m - D_n, sin b, cos b, 0) with b = fl(dE*dt)/2,
 // the frequency-independent half-angle of first_order_integral_aa.  A record is one 32-byte LDS
 // read.  Rows are padded to a multiple of 8 doubles (64-byte aligned).

@@ -104,6 +104,18 @@ FFK_HD void sincos_small(double r, double* s, double* c) {
     *c = w + (((1.0 - w) - hz) + z*z*pc);
 }
 
+// sincos_small's sine alone: the same operations in the same order, bit for bit (tests/test_sin_small_host.py).
+// With PIN only its four constants are materialised; through sincos_small<true> a caller that drops the cosine
+// still pays the cosine's six v_mov_b32 (pinned_bits is asm volatile: dead constants are not removed).
+template <bool PIN = false>
+FFK_HD double sin_small(double r) {
+    const double z = r*r;
+    double ps = fma(z, FFK_PIN(2.75573137070700676789e-06), FFK_PIN(-1.98412698298579493134e-04));
+    ps = fma(z, ps, FFK_PIN(8.33333333332248946124e-03));
+    ps = fma(z, ps, FFK_PIN(-1.66666666666666324348e-01));
+    return fma(r*z, ps, r);
+}
+
 FFK_HD unsigned low_word(double t) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return static_cast<unsigned>(__double2loint(t));
@@ -203,8 +215,9 @@ FFK_HD cplx first_order_integral(double omega, double dE, double dt) {
 // formed exactly like the reference; only the half-angle a+b differs from the reference's
 // fl(fl(omega+dE)*dt)/2 by a few ulp of (|omega|+|dE|) dt, worth ~1e-16*dt absolute in I.
 // Near a resonance (omega ~ -dE) the sum sa cb + ca sb cancels; below |h| < 2^-5 the direct
-// evaluation is used instead (a divergent but rare branch: the band is a few percent of a
-// logarithmic grid, for the half of the entries with dE < 0).
+// evaluation is used instead (a divergent branch; for an OFF-diagonal entry the band is a few
+// percent of a logarithmic grid, for the half of the entries with dE < 0 -- a caller that passes
+// dE = 0 is inside it for every frequency below 2^-4/dt).
 FFK_HD cplx first_order_integral_aa(double omega, double dE, double dt, double sa, double ca,
                                     double sb, double cb) {
     const double x = omega + dE;
@@ -227,9 +240,12 @@ FFK_HD cplx first_order_integral_aa(double omega, double dE, double dt, double s
 // and segment (PhasedFrequency): psi = e^{i omega t_g} e^{ia} and 2 sin a, 2 cos a; per entry one
 // rotation of psi by b (4 flops), 2 sin(a + b) by the addition theorem (2), a reciprocal, 3 products:
 // 13 instructions and no select, against 25 for "I, then multiply by the phase" (cos(a + b) is never
-// formed, the phase costs nothing extra, the x == 0 limit lives in the rare branch).  Near a
+// formed, the phase costs nothing extra, the x == 0 limit lives in the near branch).  Near a
 // resonance (|x dt| < 2^-4, which includes x == 0 and zero-length segments) the sine comes from the
-// short polynomial -- the sum would cancel -- as in first_order_integral_aa.
+// short polynomial -- the sum would cancel -- as in first_order_integral_aa.  The near branch is NOT
+// rare for the diagonal entries: dE = 0 there, so every frequency below 2^-4/dt takes it for every
+// segment -- the lower decades of any logarithmic grid (tools/count_near_resonance.py; the d = 4
+// kernel gives the diagonal a path of its own, ctrl_pq.hip, DESIGN.md section 6.1 "Round 8").
 // E = psi e^{ib} q with q = 2 sin(a + b)/x REAL: the d = 4 kernel (ctrl_pq.hip) never forms E; it
 // folds e^{ib} into the frequency-independent operands and contracts with q (phased_q) alone.
 struct PhasedFrequency {
@@ -249,14 +265,16 @@ FFK_HD PhasedFrequency phased_frequency(double om, double dt, cplx ph, double sa
     f.ca2 = ca + ca;
     return f;
 }
-// the real factor 2 sin(a + b)/x of an entry (x == 0: dt)
+// the real factor 2 sin(a + b)/x of an entry (x == 0: dt); phased_q_near: its form for |x| < thr alone
+FFK_HD double phased_q_near(double x, double dt) {
+    const double s = sin_small<true>(0.5*(x*dt));
+    return x == 0.0 ? dt : 2.0*s*rcp_fast(x);
+}
 FFK_HD double phased_q(const PhasedFrequency& f, double dE, double sb, double cb) {
     const double x = f.om + dE;
     double q;
     if (fabs(x) < f.thr) {
-        double s, c;
-        sincos_small<true>(0.5*(x*f.dt), &s, &c);     // (the cosine is dead code)
-        q = x == 0.0 ? f.dt : 2.0*s*rcp_fast(x);
+        q = phased_q_near(x, f.dt);
     } else {
         q = fma(f.sa2, cb, f.ca2*sb)*rcp_fast(x);
     }

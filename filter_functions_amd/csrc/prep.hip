@@ -41,7 +41,10 @@ __device__ void prologue_segment(const cplx (*V)[D], cplx (*Q)[D], cplx (*T)[D],
         st[seg_rec(e) + 3] = 0.0;
         eb = {cb, sb};
     }
-    if (lane < 2) st[2 + lane] = 0.0;
+    // [2]: the near-resonance threshold 2^-4/dt_g, phased_frequency()'s own expression (the d = 4 producers read
+    // it with the head record instead of forming it per tile and lane, ctrl_pq.hip)
+    if (lane == 0) st[2] = dt[g] > 0.0 ? 0.0625*rcp(dt[g]) : __builtin_huge_val();
+    if (lane == 1) st[3] = 0.0;
     for (int e = 4 + 4*D*D + lane; e < S; e += 64) st[e] = 0.0;
 
     // T = V^dag Q

@@ -2,6 +2,10 @@
 time (HIP events around the accumulate launch) and the whole control-matrix time.
 
     python tools/tune_accumulate.py [--d 4 --G 256 --A 3 --W 4096] [--chunks 8 12 16 ...]
+                                    [--omega-lo LO --omega-hi HI]
+
+The frequency grid is geomspace(LO, HI, W); the default ends are the bench's, 1e-2/dt.sum() and
+1e2/dt.min().  --A takes several operator counts: one process (one start-up) times them all.
 """
 import argparse
 import ctypes
@@ -19,17 +23,24 @@ from filter_functions_amd import _lib  # noqa: E402
 from filter_functions_amd.device import DevicePipeline  # noqa: E402
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--d', type=int, default=4)
     ap.add_argument('--G', type=int, default=256)
-    ap.add_argument('--A', type=int, default=3)
+    ap.add_argument('--A', type=int, nargs='+', default=[3])
     ap.add_argument('--W', type=int, default=4096)
     ap.add_argument('--reps', type=int, default=30)
     ap.add_argument('--variant', type=int, default=0, help='0 default, 1 one-wave kernel (d <= 4), 2 no in-block segment split')
     ap.add_argument('--chunks', type=int, nargs='*', default=[0, 4, 8, 11, 12, 16, 22, 32, 43, 64])
-    args = ap.parse_args()
-    d, G, A, W = args.d, args.G, args.A, args.W
+    ap.add_argument('--omega-lo', type=float, default=None, help='lowest frequency (default 1e-2/dt.sum())')
+    ap.add_argument('--omega-hi', type=float, default=None, help='highest frequency (default 1e2/dt.min())')
+    args = ap.parse_args(argv)
+    for A in args.A:
+        run(args, A)
+
+
+def run(args, A):
+    d, G, W = args.d, args.G, args.W
     rng = np.random.default_rng(42)
 
     def herm(n):
@@ -39,7 +50,9 @@ def main():
     c_opers, n_opers = herm(3), herm(A)
     c_coeffs, n_coeffs = rng.standard_normal((3, G)), rng.random((A, G))
     dt = 1 - rng.random(G)
-    omega = np.geomspace(1e-2/dt.sum(), 1e2/dt.min(), W)
+    lo = 1e-2/dt.sum() if args.omega_lo is None else args.omega_lo
+    hi = 1e2/dt.min() if args.omega_hi is None else args.omega_hi
+    omega = np.geomspace(lo, hi, W)
     basis = ff.Basis.pauli(int(np.log2(d))) if d in (2, 4, 8, 16) else ff.Basis.ggm(d)
     lib = _lib.load()
     _lib.check(lib.ffk_set_accumulate_variant(args.variant))
@@ -48,7 +61,7 @@ def main():
         _lib.check(lib.ffk_event_create(ctypes.byref(e)))
     stream = torch.cuda.current_stream().cuda_stream
     ms = ctypes.c_float()
-    print(f'd={d} G={G} A={A} W={W}')
+    print(f'd={d} G={G} A={A} W={W} omega=[{lo:.3g}, {hi:.3g}]')
     for chunks in args.chunks:
         _lib.check(lib.ffk_set_segment_chunks(chunks))
         pipe = DevicePipeline(c_opers, c_coeffs, n_opers, n_coeffs, dt, basis, omega,

@@ -1766,6 +1766,173 @@ int ffk_sequence_processes(ffk_resident* const* gates, const int32_t* slots, con
     return FFK_OK;
 }
 
+// ---- frequency shifts (second order) of many sequences from one gate table in ONE pass, under any number of spectra
+//      (ff.sequence_frequency_shifts; sequence_second_order.hip) -----------------------------------------------------
+namespace {
+
+struct SeqShiftLayout {
+    size_t offsets, index, order, tau, omega, basis, U, tab, host, S, idx, shifts, inputs_end;    // one H2D
+    size_t out, Q, outputs_end;                                                                   // one D2H
+    size_t phases, L, scale, partial, end;                                                        // device only
+};
+
+SeqShiftLayout seq_shift_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W, int n_idx,
+                                int s_ndim, int n_spectra) {
+    SeqShiftLayout L;
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N;
+    const size_t rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
+    const size_t tiles = size_t(n_spectra)*P*n_idx;
+    const int width = ffk::sequence_second_order_block_width(d, A);
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.offsets = put(4*(size_t(P) + 1));
+    L.index = put(4*n_index);
+    L.order = put(4*size_t(P));
+    L.tau = put(8*size_t(T));
+    L.omega = put(8*size_t(W));
+    L.basis = put(16*size_t(N)*dd);
+    L.U = put(16*size_t(T)*dd);
+    L.tab = put(8*size_t(T));
+    L.host = put(16*size_t(A)*N*W*size_t(n_host));
+    L.S = put(16*rows*W);
+    L.idx = put(4*size_t(n_idx));
+    L.shifts = put(8*size_t(n_spectra)*T*n_idx*nn);
+    L.inputs_end = o;
+    L.out = put(8*tiles*nn);
+    L.Q = put(16*size_t(P)*dd);
+    L.outputs_end = o;
+    L.phases = put(16*size_t(T)*W);
+    L.L = put(8*size_t(T)*nn);
+    L.scale = put(16*rows*W);
+    L.partial = put(8*size_t((W + width - 1)/width)*tiles*nn);
+    L.end = o;
+    return L;
+}
+
+bool seq_shift_shape_ok(int T, int P, int d, int A, int N, int W, int n_idx, int s_ndim, int n_spectra) {
+    return seq_infid_shape_ok(T, P, d, A, N, W) && W >= 2 && (s_ndim == 1 || s_ndim == 2) && n_idx >= 1 &&
+           n_idx <= A && n_spectra >= 1 && n_spectra <= 65535;
+}
+
+}  // namespace
+
+size_t ffk_sequence_frequency_shifts_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                                     int n_idx, int s_ndim, int n_spectra) {
+    if (!seq_shift_shape_ok(T, P, d, A, N, W, n_idx, s_ndim, n_spectra) || n_index < P || n_host < 0 || n_host > T)
+        return 0;
+    return seq_shift_layout(T, P, size_t(n_index), n_host, d, A, N, W, n_idx, s_ndim, n_spectra).end;
+}
+
+int ffk_sequence_frequency_shifts(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                  const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                                  const int32_t* index, int P, const double* omega, int W, const double* basis,
+                                  int hermitian_basis, int d, int A, int N, const double* spectrum, int s_ndim,
+                                  int n_spectra, const int32_t* idx, int n_idx, const double* gate_shifts, double* out,
+                                  int32_t* not_finite, double* total_propagators) {
+    FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis && spectrum && idx &&
+                gate_shifts && out && not_finite, "NULL argument");
+    FFK_REQUIRE(ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A),
+                "unsupported shape d=%d N=%d A=%d (need (d, N) = (2, 4) or (4, 16), 1 <= A <= 4)", d, N, A);
+    FFK_REQUIRE(hermitian_basis != 0, "the batched rule needs a Hermitian basis");
+    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 2,
+                "empty or oversized axis: T=%d P=%d W=%d (need W >= 2)", T, P, W);
+    FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
+    FFK_REQUIRE(n_spectra >= 1 && n_spectra <= 65535, "n_spectra = %d, need 1 ... 65535", n_spectra);
+    if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d, true)) return rc;
+    for (int i = 0; i < n_idx; ++i)
+        for (int m = 0; m < i; ++m)
+            FFK_REQUIRE(idx[i] != idx[m], "idx[%d] = idx[%d] = %d: the selected operators must be distinct", m, i,
+                        idx[i]);
+    FFK_REQUIRE(offsets[0] == 0, "offsets[0] = %d, expected 0", offsets[0]);
+    for (int p = 0; p < P; ++p)
+        FFK_REQUIRE(offsets[p + 1] > offsets[p], "offsets not increasing at sequence %d (%d -> %d)", p, offsets[p],
+                    offsets[p + 1]);
+    const size_t n_index = size_t(offsets[P]);
+    for (size_t g = 0; g < n_index; ++g)
+        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
+    const size_t tiles = size_t(n_spectra)*P*n_idx, members = size_t(n_spectra)*P;
+    FFK_REQUIRE(tiles <= (size_t(1) << 26), "%zu tiles exceed one pass", tiles);
+    const size_t s_rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    std::vector<const unsigned char*> tab;
+    int n_host = 0;
+    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
+    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    const SeqShiftLayout L = seq_shift_layout(T, P, n_index, n_host, d, A, N, W, n_idx, s_ndim, n_spectra);
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N, row = 16*size_t(A)*N*W;
+    // the sequences sorted by length, longest first (stable): the kernels deal them out in this order
+    std::vector<int32_t> order(P);
+    for (int p = 0; p < P; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [offsets](int32_t a, int32_t b) {
+        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
+    });
+    PinLease pin;
+    if (int rc = pin.take(L.outputs_end, dev)) return rc;
+    unsigned char* hp = pin.ptr();
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    void* base = nullptr;
+    if (int rc = arena_reserve(L.end, &base)) return rc;
+    unsigned char* dp = static_cast<unsigned char*>(base);
+    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
+    std::memcpy(hp + L.index, index, 4*n_index);
+    std::memcpy(hp + L.order, order.data(), 4*size_t(P));
+    std::memcpy(hp + L.tau, tau, 8*size_t(T));
+    std::memcpy(hp + L.omega, omega, 8*size_t(W));
+    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
+    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
+    place_host_rows(&tab, dp + L.host, row);
+    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
+    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    stage_spectrum(spectrum, true, s_rows*W, idx, n_idx, hp + L.S, hp + L.idx);
+    std::memcpy(hp + L.shifts, gate_shifts, 8*size_t(n_spectra)*T*n_idx*nn);
+    StreamDrain drain{s};
+    auto at = [dp](size_t off) { return dp + off; };
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    const cplx* dU = reinterpret_cast<const cplx*>(at(L.U));
+    const double* dTau = reinterpret_cast<const double*>(at(L.tau));
+    const double* dOmega = reinterpret_cast<const double*>(at(L.omega));
+    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
+    const int32_t* dIndex = reinterpret_cast<const int32_t*>(at(L.index));
+    const int32_t* dOrder = reinterpret_cast<const int32_t*>(at(L.order));
+    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.idx));
+    const cplx* dBasis = reinterpret_cast<const cplx*>(at(L.basis));
+    const cplx* const* dTab = reinterpret_cast<const cplx* const*>(at(L.tab));
+    cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
+    double* dL = reinterpret_cast<double*>(at(L.L));
+    cplx* dQ = reinterpret_cast<cplx*>(at(L.Q));
+    cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
+    if (d == 2)
+        FFK_HIP(ffk::launch_sequences_front(dU, dTau, dOmega, T, W, dOff, dIndex, P, dBasis, dPh, dL, dQ, s));
+    else
+        FFK_HIP(ffk::launch_sequences4_front(dU, dTau, dOmega, T, W, dOff, dIndex, P, dBasis, dPh, dL, dQ, s));
+    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(s_rows), W, dOmega, W, 0, dScale,
+                                         s));
+    FFK_HIP(ffk::launch_sequence_second_order(d, dPh, dTab, dL, dOff, dIndex, dOrder, P, T, A, W, dScale, s_ndim,
+                                              n_spectra, dIdx, n_idx, reinterpret_cast<const double*>(at(L.shifts)),
+                                              reinterpret_cast<double*>(at(L.partial)),
+                                              reinterpret_cast<double*>(at(L.out)), s));
+    FFK_HIP(hipMemcpyAsync(hp + L.out, dp + L.out, L.outputs_end - L.out, hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    if (int rc = kernel_fault_status()) return rc;
+    std::memcpy(out, hp + L.out, 8*tiles*nn);
+    // a (spectrum, sequence) whose tiles hold a NaN or Inf
+    const double* values = reinterpret_cast<const double*>(hp + L.out);
+    const size_t member = size_t(n_idx)*nn;
+    for (size_t m = 0; m < members; ++m) {
+        int32_t bad = 0;
+        for (size_t e = 0; e < member && !bad; ++e) {
+            const double v = values[m*member + e];
+            bad = !(v - v == 0.0);
+        }
+        not_finite[m] = bad;
+    }
+    if (total_propagators) std::memcpy(total_propagators, hp + L.Q, 16*size_t(P)*dd);
+    return FFK_OK;
+}
+
 }  // extern "C"
 
 #if defined(FFK_HOST_SANITIZE)
@@ -1955,6 +2122,14 @@ extern "C" int ffk_selftest_host(int rounds, unsigned seed, char* report, int re
                 (!ascending(CL) || CL.part + 8*size_t(ffk::correlation_slabs(W, nullptr))*si*total > CL.end ||
                  CL.end > ffk_sequence_correlation_infidelities_workspace_bytes(T, P, n_index, n_host, 2, As, 4, W, si, sc)))
                 return -16;
+            // the frequency-shift pass of the sequences: what the query reports, the partial tiles inside it
+            const int sn = pick(1, 2), ks = pick(1, 5);
+            if (W >= 2) {
+                const SeqShiftLayout HL = seq_shift_layout(T, P, size_t(n_index), n_host, 2, As, 4, W, si, sn, ks);
+                if (!ascending(HL) || HL.partial + 8*size_t((W + 63)/64)*ks*P*si*16 > HL.end ||
+                    HL.end != ffk_sequence_frequency_shifts_workspace_bytes(T, P, n_index, n_host, 2, As, 4, W, si, sn, ks))
+                    return -17;
+            }
             const int Np = N < 16 ? N : 16, hosts = pick(0, P);
             const ProcLayout PL = proc_layout(P, hosts, A, Np, W, d, n_idx, s_ndim, false, true, true, true);
             if (!ascending(PL) || PL.end != ffk_resident_batch_processes_workspace_bytes(P, hosts, A, Np, W, d, n_idx, s_ndim))

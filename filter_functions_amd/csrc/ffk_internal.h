@@ -406,6 +406,22 @@ hipError_t launch_sequences_gamma(int d, const cplx* phases, const cplx* const* 
                                   int A, int W, const cplx* scale, int s_ndim, int n_spectra, const int32_t* idx,
                                   int n_idx, double* partial, double* gamma, hipStream_t stream);
 
+// ---- sequence_second_order.hip ----------------------------------------------------------------
+// Frequency shifts of the sequences of such a pass (d = 2 or 4), after the front launch of its dimension: one forward
+// walk of each sequence and the sum of the frequency blocks' partial tiles in index order (two launches whatever P and
+// n_spectra; grid z carries the spectra beyond sequence_second_order_spectra_per_walk()).  scale as for
+// launch_sequences_gamma; gate_shifts (n_spectra, T, n_idx, N, N) f64 the gates' own frequency shifts; partial
+// (ceil(W / block width), P, n_spectra, n_idx, N, N) f64 scratch; out (n_spectra, P, n_idx, N, N) f64.  idx holds
+// distinct operators.  The block width depends on d and A alone.
+int sequence_second_order_block_width(int d, int A);
+int sequence_second_order_spectra_per_walk();
+bool sequence_second_order_staged(int d, int T, int A);
+hipError_t launch_sequence_second_order(int d, const cplx* phases, const cplx* const* Rtab, const double* Lpulse,
+                                        const int32_t* offsets, const int32_t* index, const int32_t* order, int P,
+                                        int T, int A, int W, const cplx* scale, int s_ndim, int n_spectra,
+                                        const int32_t* idx, int n_idx, const double* gate_shifts, double* partial,
+                                        double* out, hipStream_t stream);
+
 // ---- correlations.hip -------------------------------------------------------------------------
 // Pulse-correlation infidelities of many sequences from one gate table (d = 2, N = 4, A <= 4, at most
 // correlation_max_length() positions each), after launch_sequences_front.  Prefix: Qc (n_index, N, N) f64, the

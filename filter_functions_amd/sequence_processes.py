@@ -223,7 +223,62 @@ _SHARED = r"""
     matrices are never written, and the K spectra cost one walk of the sequences.  A sequence's result is the same
     bits alone or among others, in any pass split, stacked or one spectrum at a time.  Everything else --
     cross-spectra, other dimensions, ineligible gate sets -- and every sequence whose result is not finite evaluates
-    the loop's expression inside the call.  Second order and pulse correlations are not offered."""
+    the loop's expression inside the call.  With ``second_order=True`` (cumulant functions and error transfer
+    matrices) the loop's concatenation is ``ff.concatenate(..., calc_second_order_FF=True, omega=omega)`` and its
+    functions are called with ``second_order=True``: the first-order cumulant functions are computed as without the
+    keyword, the frequency shifts come from :func:`ff.sequence_frequency_shifts
+    <filter_functions_amd.sequence_second_order.sequence_frequency_shifts>` (whose routing and cache behaviour apply)
+    and their contribution to every tile is added by one call of ``ffk_cumulant_function_second_order``.  Pulse
+    correlations are not offered."""
+
+
+def _second_order_loop(stage, gates, indices, spectra, omega, n_oper_identifiers, want_U):
+    """The loop's expression with ``second_order=True`` for every sequence under every spectrum."""
+    from . import numeric
+    from .sequence_second_order import _concatenated as concatenated
+    single = numeric.calculate_cumulant_function if stage == 'cumulant_function' else numeric.error_transfer_matrix
+    pulses = [concatenated(gates, i, omega) for i in indices]
+    out = np.stack([np.stack([single(pulse, S, omega, n_oper_identifiers, second_order=True) for pulse in pulses])
+                    for S in spectra])
+    return out, np.stack([np.array(pulse.total_propagator) for pulse in pulses]) if want_U else None
+
+
+def _second_order(stage, gates, sequences, spectrum, omega, n_oper_identifiers, stacked, return_propagators):
+    """First-order cumulant functions as without the keyword, frequency shifts from ``ff.sequence_frequency_shifts``
+    and the second-order term of every tile added by one call of ``ffk_cumulant_function_second_order``: what
+    ``processes._second_order_cumulants`` does for single pulses."""
+    from . import numeric, sequence_second_order
+    from .batch_second_order import _same_basis
+    gates, sequences = list(gates), list(sequences)
+    first = _results('cumulant_function', gates, sequences, spectrum, omega, n_oper_identifiers, stacked,
+                     return_propagators)
+    K, total = first if return_propagators else (first, None)
+    same = all(_same_basis(gates[0].basis, g.basis) for g in gates[1:])
+    if not same:
+        # (gates of several bases: no single basis to contract with -- the loop's expression)
+        values, total = _second_order_loop(stage, gates, index_arrays(sequences, len(gates)),
+                                           stacked_spectra(spectrum, stacked), omega, n_oper_identifiers,
+                                           bool(return_propagators))
+        values = values if stacked else values[0]
+        return (values, total) if return_propagators else values
+    delta = sequence_second_order.sequence_frequency_shifts(gates, sequences, spectrum, omega, n_oper_identifiers,
+                                                            stacked)
+    if np.shape(delta) != np.shape(K):
+        raise ValueError('Frequency shifts not same shape as decay amplitudes')
+    basis = gates[0].basis
+    N, d = np.shape(basis)[:2]
+    numeric._check_d(d)
+    C = as_c128(np.asarray(basis))
+    tiles = np.ascontiguousarray(as_f64(K)).reshape(-1, N, N).copy()
+    shifts = np.ascontiguousarray(as_f64(delta).reshape(-1, N, N))
+    check(_lib.load().ffk_cumulant_function_second_order(shifts.ctypes.data, len(shifts), N, d, C.ctypes.data,
+                                                         tiles.ctypes.data))
+    K = tiles.reshape(np.shape(K))
+    if stage == 'error_transfer_matrix':
+        flat = K.reshape((-1,) + K.shape[(2 if stacked else 1):])
+        K = np.stack([numeric.error_transfer_matrix(cumulant_function=k) for k in flat]).reshape(
+            K.shape[:(2 if stacked else 1)] + (N, N))
+    return (K, total) if return_propagators else K
 
 
 def sequence_decay_amplitudes(gates, sequences, spectrum, omega, n_oper_identifiers=None, stacked=False,
@@ -239,23 +294,29 @@ def sequence_decay_amplitudes(gates, sequences, spectrum, omega, n_oper_identifi
 
 
 def sequence_cumulant_functions(gates, sequences, spectrum, omega, n_oper_identifiers=None, stacked=False,
-                                return_propagators=False):
+                                return_propagators=False, second_order=False):
     r"""Cumulant functions :math:`\mathcal{K}_{\alpha\beta}` of many sequences of gates drawn from one gate set, the
     shape of :func:`sequence_decay_amplitudes`:
 
     ``np.stack([numeric.calculate_cumulant_function(ff.concatenate(np.asarray(gates, dtype=object)[s], omega=omega),
     spectrum, omega, n_oper_identifiers) for s in sequences])``."""
+    if second_order:
+        return _second_order('cumulant_function', gates, sequences, spectrum, omega, n_oper_identifiers, stacked,
+                             return_propagators)
     return _results('cumulant_function', gates, sequences, spectrum, omega, n_oper_identifiers, stacked,
                     return_propagators)
 
 
 def sequence_error_transfer_matrices(gates, sequences, spectrum, omega, n_oper_identifiers=None, stacked=False,
-                                     return_propagators=False):
+                                     return_propagators=False, second_order=False):
     r"""Error transfer matrices :math:`\exp\mathcal{K}` of many sequences of gates drawn from one gate set, shape
     (P, N, N):
 
     ``np.stack([ff.error_transfer_matrix(ff.concatenate(np.asarray(gates, dtype=object)[s], omega=omega), spectrum,
     omega, n_oper_identifiers) for s in sequences])``."""
+    if second_order:
+        return _second_order('error_transfer_matrix', gates, sequences, spectrum, omega, n_oper_identifiers, stacked,
+                             return_propagators)
     return _results('error_transfer_matrix', gates, sequences, spectrum, omega, n_oper_identifiers, stacked,
                     return_propagators)
 

@@ -1,0 +1,199 @@
+"""Frequency shifts (second order) of many gate sequences given as index arrays into one gate set
+(``ffk_sequence_frequency_shifts``, include/ffk.h).
+
+``ff.sequence_frequency_shifts(gates, sequences, spectrum, omega)`` is ``np.stack`` of the loop over
+``numeric.calculate_frequency_shifts`` on ``ff.concatenate(gates[s], calc_second_order_FF=True, omega=omega)``: the
+index-array front end of :mod:`~filter_functions_amd.sequence_processes` for the coherent part of a sequence's error.
+The loop forms the second-order filter function of every sequence, (A, A, N, N, W) complex, and copies it to the host;
+the batched route integrates the rotated concatenation rule of that filter function position by position, so that
+nothing of size W N^2 exists: the gates' own frequency shifts come from one ``ff.frequency_shifts`` call per spectrum,
+and one walk of each sequence adds their rotations and the Gram matrices of the first-order rule's summands with their
+running sum, for every spectrum of the call (``stacked=True``).
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib, util
+from ._lib import as_c128, as_f64, check
+from .batch import MAX_PULSES, PASS_BYTES, split_passes
+from .sequence_infidelities import _on_grid, eligibility, index_arrays
+from .sequence_processes import _real_weights, stacked_spectra
+from .sequences import pack_sequences, resident_source
+
+__all__ = ['sequence_frequency_shifts']
+
+#: Spectra that share one walk of the sequences (``sequence_second_order_spectra_per_walk``); further ones repeat it.
+SPECTRA_PER_WALK = 2
+
+
+def block_width(d, A):
+    """Frequencies of one block of the walk (``sequence_second_order_block_width``): a function of d and A alone."""
+    return 64 if d == 2 or A <= 2 else 32
+
+
+def _up(nbytes):
+    return -(-nbytes//256)*256
+
+
+def pass_bytes(max_length, d, A, W, n_idx, n_spectra):
+    """Device bytes one sequence adds to a pass at most: its positions, propagator, its tiles of the result and the
+    frequency blocks' partial tiles."""
+    N, dd = d*d, d*d
+    tiles = n_spectra*n_idx
+    blocks = -(-W//block_width(d, A))
+    return 12 + 4*max_length + 16*dd + 8*N*N*tiles*(1 + blocks)
+
+
+def table_bytes(n_gates, d, A, W, n_idx, n_spectra, s_ndim):
+    """Device bytes of what a pass holds once whatever its sequences: the gate table, the gates' phases, propagators,
+    Liouville representations and frequency shifts, the spectra and their weights, the basis."""
+    N, dd = d*d, d*d
+    rows = n_spectra*(1 if s_ndim == 1 else n_idx)
+    return (n_gates*(16*A*N*W + 16*W + 8*N*N + 16*dd + 16 + 8*N*N*n_spectra*n_idx) + 16*N*dd + 8*W + 32*rows*W
+            + 4*n_idx + 20*256)
+
+
+def _run_pass(gates, indices, plan, omega, S, idx, shifts, want_U):
+    """One call of ``ffk_sequence_frequency_shifts`` over the sequences *indices* (int32 arrays into *gates*), the
+    spectra S (K, W) or (K, n_idx, W) and the gates' own frequency shifts (K, T, n_idx, N, N): (values (K, P, n_idx,
+    N, N), not finite (K, P), total propagators (P, d, d) or None)."""
+    d, N, A = plan['d'], plan['N'], plan['A']
+    W, P, K = len(omega), len(indices), len(S)
+    used = np.unique(np.concatenate(indices))
+    slot_of = np.full(len(gates), -1, dtype=np.int32)
+    slot_of[used] = np.arange(len(used), dtype=np.int32)
+    table_gates = [gates[k] for k in used]
+    sources = [resident_source(g, d, W, N, A) for g in table_gates]
+    host = [g for g, src in zip(table_gates, sources) if src is None]
+    table = as_c128(np.array([g.get_control_matrix(omega) for g in host])) if host else None
+    handles = (ctypes.c_void_p*len(table_gates))(*[None if src is None else src[0].value for src in sources])
+    slots = np.array([-1 if src is None else src[1] for src in sources], dtype=np.int32)
+    U = as_c128(np.array([g.total_propagator for g in table_gates]))
+    tau = np.array([g.tau for g in table_gates], dtype=np.float64)
+    offsets, index, _ = pack_sequences([slot_of[i] for i in indices])
+    basis = as_c128(np.asarray(plan['basis']))
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    n_idx = len(idx)
+    own = as_f64(np.ascontiguousarray(np.asarray(shifts)[:, used]))
+    out = np.empty((K, P, n_idx, N, N), dtype=np.float64)
+    flags = np.zeros((K, P), dtype=np.int32)
+    total = np.empty((P, d, d), dtype=np.complex128) if want_U else None
+    check(_lib.load().ffk_sequence_frequency_shifts(
+        handles, slots.ctypes.data, None if table is None else table.ctypes.data, U.ctypes.data, tau.ctypes.data,
+        len(table_gates), offsets.ctypes.data, index.ctypes.data, P, omega.ctypes.data, W, basis.ctypes.data, 1, d, A,
+        N, S.ctypes.data, S.ndim - 1, K, idx.ctypes.data, n_idx, own.ctypes.data, out.ctypes.data, flags.ctypes.data,
+        None if total is None else total.ctypes.data))
+    return out, flags != 0, total
+
+
+def _concatenated(gates, sequence, omega):
+    """The loop's pulse of one sequence."""
+    import filter_functions_amd as ff         # (the public names, as a caller's loop reads them)
+    table = np.empty(len(gates), dtype=object)
+    table[:] = gates
+    return ff.concatenate(table[sequence], calc_second_order_FF=True, omega=omega)
+
+
+def _single(pulse, spectrum, omega, n_oper_identifiers):
+    from . import numeric
+    return numeric.calculate_frequency_shifts(pulse, spectrum, omega, n_oper_identifiers)
+
+
+def _loop(gates, indices, spectra, omega, n_oper_identifiers, want_U):
+    """The loop's expression for every sequence under every spectrum: (values (K, P, ...), total propagators)."""
+    pulses = [_concatenated(gates, i, omega) for i in indices]
+    out = np.stack([np.stack([_single(pulse, S, omega, n_oper_identifiers) for pulse in pulses]) for S in spectra])
+    return out, np.stack([np.array(pulse.total_propagator) for pulse in pulses]) if want_U else None
+
+
+def _gate_shifts(gates, spectrum, omega, n_oper_identifiers):
+    """The gates' own frequency shifts under one spectrum, (T, n_idx, N, N)."""
+    from .batch_second_order import frequency_shifts
+    return frequency_shifts(gates, spectrum, omega, n_oper_identifiers)
+
+
+def sequence_frequency_shifts(gates, sequences, spectrum, omega, n_oper_identifiers=None, stacked=False,
+                              return_propagators=False):
+    r"""Frequency shifts :math:`\Delta_{\alpha\beta,kl}` of many sequences of gates drawn from one gate set:
+
+    ``np.stack([numeric.calculate_frequency_shifts(ff.concatenate(np.asarray(gates, dtype=object)[s],
+    calc_second_order_FF=True, omega=omega), spectrum, omega, n_oper_identifiers) for s in sequences])``
+
+    of shape (P, n_idx, N, N), or (P, n_idx, n_idx, N, N) for a cross-spectrum.
+
+    *gates* is a sequence of T ``PulseSequence`` objects, *sequences* a list of P one-dimensional integer arrays of
+    indices into it, read as :func:`ff.sequence_infidelities <filter_functions_amd.sequence_infidelities.
+    sequence_infidelities>` reads them (negative indices wrap, others out of range raise IndexError, an empty sequence
+    ValueError, an index that is no integer TypeError).  Values and exceptions are the loop's.  With *stacked* the
+    spectrum carries a leading axis of K spectra -- (K, n_omega), (K, n_idx, n_omega) or (K, n_idx, n_idx, n_omega);
+    K = 0 raises ValueError -- and the result a leading axis K: ``np.stack`` of the calls with ``spectrum[k]``, each
+    parsed in order.  With *return_propagators* the total propagators (P, d, d) are returned as well.
+
+    Routing, once per call.  The batched route is taken by the gate sets :func:`ff.sequence_infidelities` takes (all
+    gates d = 2 or all d = 4, one Hermitian traceless basis of d^2 elements, the same one to four noise operators,
+    total propagators known) under spectra of one or two dimensions without imaginary part, on at least two
+    frequencies, with at least one operator selected and none selected twice.  Gates without a control matrix on the
+    grid are completed first by one ``ff.get_filter_functions`` call.  The gates' own frequency shifts come from
+    ``ff.frequency_shifts(gates, spectrum[k], omega, n_oper_identifiers)``, one call per spectrum, whose routing and
+    cache behaviour apply: batched members of that call end WITHOUT ``filter_function_2`` cached (their eigensystems
+    are cached and ``gate.omega`` is set), where the loop would leave every gate with it.  No ``PulseSequence`` is
+    created for a sequence and resident gates are read in place.  A pass is one H2D copy, a fixed number of launches
+    whatever P and K, and one D2H copy; neither a second-order filter function nor a sequence's control matrix is
+    written to memory.  Two spectra share one walk of the sequences, further pairs repeat it inside the same launch.
+    A sequence's result is the same bits alone or among others, in any pass split, stacked or one spectrum at a time,
+    and a sequence of one gate returns that gate's frequency shifts.  Everything else -- cross-spectra, other
+    dimensions, ineligible gate sets -- and every (spectrum, sequence) whose result is not finite evaluates the loop's
+    expression inside the call.  Pulse correlations are not offered."""
+    from .pulse_sequence import PulseSequence
+    gates = list(gates)
+    for gate in gates:
+        if not isinstance(gate, PulseSequence):
+            raise TypeError('Can only concatenate PulseSequences!')
+    indices = index_arrays(sequences, len(gates))
+    if not indices:
+        raise ValueError('Need at least one sequence.')
+    spectra = stacked_spectra(spectrum, stacked)
+    want_U = bool(return_propagators)
+
+    def answer(values, total):
+        values = values if stacked else values[0]
+        return (values, total) if want_U else values
+    # routing, once per call: the gate set, then the spectra
+    plan = eligibility(gates) if all(S.ndim in (1, 2) for S in spectra) and len(omega) >= 2 else None
+    if plan is not None:
+        missing = [g for g in gates if not _on_grid(g, omega)]
+        if missing:
+            from .batch import get_filter_functions
+            get_filter_functions(missing, omega)
+        if not all('total_propagator' in g._data for g in gates):
+            plan = None
+    S = None
+    if plan is not None:
+        omega = as_f64(omega)
+        idx = np.asarray(util.get_indices_from_identifiers(gates[0].n_oper_identifiers, n_oper_identifiers))
+        if len(idx) and len(set(idx.tolist())) == len(idx):
+            S = _real_weights([util.parse_spectrum(one, omega, idx) for one in spectra])
+    if S is None:
+        return answer(*_loop(gates, indices, spectra, omega, n_oper_identifiers, want_U))
+    d, N, A, W, P, K, n_idx = plan['d'], plan['N'], plan['A'], len(omega), len(indices), len(S), len(idx)
+    shifts = np.stack([_gate_shifts(gates, one, omega, n_oper_identifiers) for one in spectra])
+    values = np.empty((K, P, n_idx, N, N), dtype=np.float64)
+    bad = np.zeros((K, P), dtype=bool)
+    total = np.empty((P, d, d), dtype=np.complex128) if want_U else None
+    longest = max(len(i) for i in indices)
+    per_sequence = pass_bytes(longest, d, A, W, n_idx, K)
+    budget = max(PASS_BYTES - table_bytes(len(gates), d, A, W, n_idx, K, S.ndim - 1), 2*per_sequence)
+    for chunk in split_passes(list(range(P)), per_sequence, budget, MAX_PULSES):
+        got, flags, U = _run_pass(gates, [indices[i] for i in chunk], plan, omega, S, idx, shifts, want_U)
+        values[:, chunk[0]:chunk[-1] + 1] = got
+        bad[:, chunk[0]:chunk[-1] + 1] = flags
+        if U is not None:
+            total[chunk[0]:chunk[-1] + 1] = U
+    # the members whose result is not finite: what the loop does
+    if bad.any():
+        for i in np.flatnonzero(bad.any(axis=0)):
+            pulse = _concatenated(gates, indices[i], omega)
+            for k in np.flatnonzero(bad[:, i]):
+                values[k, i] = _single(pulse, spectra[k], omega, n_oper_identifiers)
+    return answer(values, total)

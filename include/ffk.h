@@ -802,6 +802,33 @@ int ffk_sequence_processes(ffk_resident* const* gates, const int32_t* slots, con
                            int s_ndim, int n_spectra, const int32_t* idx, int n_idx, int stage, double* out,
                            int32_t* not_finite, double* total_propagators);
 
+/* ---- frequency shifts (second order) of many gate sequences from one gate set in ONE pass, under any number of
+ *      spectra (ff.sequence_frequency_shifts) ----
+ * Sequences, gates, slots, gate_table, gate_propagators, tau, omega, basis, spectrum, s_ndim, n_spectra and idx as for
+ * ffk_sequence_processes (Hermitian basis; (d, N) = (2, 4) or (4, 16), 1 <= A <= 4; W >= 2; real weights of one or
+ * two dimensions); the operators in idx must be distinct.  gate_shifts (n_spectra, T, n_idx, N, N) f64 host: the
+ * gates' own frequency shifts under each spectrum (ffk_batch_frequency_shifts, ff.frequency_shifts).  out
+ * (n_spectra, P, n_idx, N, N) f64 host: the frequency shifts of the sequences, i.e. the integral of the rotated
+ * concatenation rule of the second-order filter function,
+ *     sum_g [ Lam_g^T gate_shifts[k_g] Lam_g + sum_w c_w S(w) Re(conj(Rs_g[k, w]) Cum_{g-1}[l, w]) ],
+ * Lam_g the Liouville matrix of the propagator before position g, Rs_g the first-order rule's summand and Cum its
+ * running sum.  Neither a second-order filter function nor a sequence's control matrix is written to memory.
+ * not_finite (n_spectra, P) int32: 1 where a sequence's tiles under a spectrum hold a NaN or Inf.  total_propagators
+ * (P, d, d) c128 host may be NULL.  One H2D copy, a fixed number of launches whatever P and n_spectra -- the front,
+ * the weights, one forward walk of the sequences (two spectra share a walk, grid z carries the further pairs), the sum
+ * of the frequency blocks' partial tiles in block order --, one D2H copy.  Arena workspace, no result handle.  A
+ * sequence's result is the same bits whatever else is in the pass, whatever its place and however many spectra the
+ * call carries; a sequence of one gate returns that gate's row of gate_shifts.  Bad arguments: FFK_EINVAL before
+ * anything touches the device.  The workspace query needs no GPU (0: unsupported shape). */
+size_t ffk_sequence_frequency_shifts_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                                     int n_idx, int s_ndim, int n_spectra);
+int ffk_sequence_frequency_shifts(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                  const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                                  const int32_t* index, int P, const double* omega, int W, const double* basis,
+                                  int hermitian_basis, int d, int A, int N, const double* spectrum, int s_ndim,
+                                  int n_spectra, const int32_t* idx, int n_idx, const double* gate_shifts, double* out,
+                                  int32_t* not_finite, double* total_propagators);
+
 /* ---- one-sided all-gather of the F blocks over xGMI (frequency-sharded step; the
  *      reference has no multi-device path: numeric.py:846-869 is embarrassingly parallel in omega
  *      and this is the exchange that reassembles F(omega) for util.integrate, util.py:880-906) ----

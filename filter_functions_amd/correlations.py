@@ -11,15 +11,14 @@ eight launches whatever the number of sequences, one D2H copy of the ragged resu
 concatenation rule nor the pulse-correlation filter function (G, G, A, A, W) exist anywhere.  Every other sequence
 runs the loop's expression.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib, util
+from ._gate_table import staged_gates
 from ._lib import as_c128, as_f64, check
 from ._resident import spectrum_arguments
 from .batch import MAX_PULSES, PASS_BYTES, split_passes
-from .sequences import _gate_source, _plan, group_plans, pack_sequences
+from .sequences import _plan, group_plans, pack_sequences
 
 __all__ = ['correlation_infidelities']
 
@@ -95,13 +94,7 @@ def _run_pass(plans, members):
             if id(gate) not in slot_of:
                 slot_of[id(gate)] = len(gates)
                 gates.append(gate)
-    sources = [_gate_source(g, W, A) for g in gates]
-    host = [g for g, src in zip(gates, sources) if src is None]
-    table = as_c128(np.array([g.get_control_matrix(omega) for g in host])) if host else None
-    handles = (ctypes.c_void_p*len(gates))(*[None if src is None else src[0].value for src in sources])
-    slots = np.array([-1 if src is None else src[1] for src in sources], dtype=np.int32)
-    U = as_c128(np.array([g.total_propagator for g in gates]))
-    tau = np.array([g.tau for g in gates], dtype=np.float64)
+    handles, slots, table, U, tau = staged_gates(gates, omega, 2, 4, A)
     indices = [np.array([slot_of[id(g)] for g in plan['distinct']], dtype=np.int32)[plan['index']] for plan in group]
     offsets, index, _ = pack_sequences(indices)
     out_offsets = output_offsets(lengths)

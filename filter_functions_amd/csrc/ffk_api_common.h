@@ -8,6 +8,8 @@
 //   ffk_api_sequence.hip  concatenation rule, decay amplitudes, cumulant function, expm (SURVEY 8 f)
 //   ffk_api_resident.hip  resident results behind PulseSequence / ff.infidelity, the batched, sequence and
 //                         process passes on resident handles; host self test
+//     ffk_api_gate_table.h  (included by it alone) the gate table that its passes over many sequences share: the
+//                         view of their common arguments, checks, layout head, staging, device pointers
 //   ffk_api_frozen.hip    second order and gradient (outside SURVEY 8, frozen since round 2)
 //   ffk_api_batch.hip     many pulses of one shape in one pass of the pipeline (ffk_pipeline_batch_dev)
 //   ffk_api_batch_grad.hip  the gradient of the filter function / infidelity of many pulses in one pass

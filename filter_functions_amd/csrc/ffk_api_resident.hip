@@ -5,6 +5,7 @@
 #include <thread>
 
 #include "ffk_api_common.h"
+#include "ffk_api_gate_table.h"
 
 
 namespace {
@@ -225,7 +226,8 @@ int member_control_matrix(const ffk_resident* g, int slot, int device, int d, in
 }
 
 // Where each of n control matrices lies on the device: in its handle (member_control_matrix), or -- no handle -- in a
-// row of the host table that the pass uploads: left NULL here and counted, placed by place_host_rows.
+// row of the host table that the pass uploads: left NULL here and counted, placed by place_host_rows
+// (ffk_api_gate_table.h).
 int locate_control_matrices(ffk_resident* const* handles, const int32_t* slots, int n, int device, int d, int A, int N,
                             int W, const char* what, std::vector<const unsigned char*>* at, int* n_host) {
     at->assign(size_t(n), nullptr);
@@ -238,12 +240,12 @@ int locate_control_matrices(ffk_resident* const* handles, const int32_t* slots, 
     }
     return FFK_OK;
 }
-void place_host_rows(std::vector<const unsigned char*>* at, const unsigned char* table, size_t row_bytes) {
-    for (const unsigned char*& p : *at)
-        if (!p) {
-            p = table;
-            table += row_bytes;
-        }
+// ... of the gates of a gate table, whose host table is then required
+int locate_gates(const GateTable& g, int device, std::vector<const unsigned char*>* at, int* n_host) {
+    if (int rc = locate_control_matrices(g.gates, g.slots, g.T, device, g.d, g.A, g.N, g.W, "gate", at, n_host))
+        return rc;
+    FFK_REQUIRE(*n_host == 0 || g.gate_table, "gate_table is NULL but %d gate(s) have no handle", *n_host);
+    return FFK_OK;
 }
 
 }  // namespace
@@ -890,8 +892,10 @@ int ffk_resident_infidelity(ffk_resident* r, const double* spectrum, int s_ndim,
 // ---- many sequences from one gate table in ONE pass (ff.concatenate_sequences; sequences.hip) ----------------
 namespace {
 
+// (every layout of these passes: the gate table first -- ffk_api_gate_table.h --, then what the pass adds)
 struct SeqLayout {
-    size_t offsets, index, order, tau, omega, basis, U, tab, host, S, idx, inputs_end;    // one H2D
+    GateTableLayout table;
+    size_t S, idx, inputs_end;                                                          // one H2D
     size_t Q, F, infid, outputs_end;                                                    // one D2H
     size_t R, phases, L, end;                                                           // device only
 };
@@ -901,15 +905,7 @@ SeqLayout seq_layout(int T, int P, size_t n_index, int n_host, int d, int A, int
     const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
     size_t o = 0;
     auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
-    L.offsets = put(4*(size_t(P) + 1));
-    L.index = put(4*n_index);
-    L.order = put(4*size_t(P));
-    L.tau = put(8*size_t(T));
-    L.omega = put(8*size_t(W));
-    L.basis = put(16*size_t(N)*dd);
-    L.U = put(16*size_t(T)*dd);
-    L.tab = put(8*size_t(T));
-    L.host = put(row*size_t(n_host));
+    L.table = gate_table_layout(put, T, P, n_index, n_host, d, A, N, W);
     L.S = put(16*sh.rows*W);
     L.idx = put(4*size_t(n_idx));
     L.inputs_end = o;
@@ -942,21 +938,14 @@ int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const
                                        int A, int N, const double* spectrum, int s_ndim, int spectrum_is_real,
                                        const int32_t* idx, int n_idx, int d_infidelity, double* total_propagators,
                                        double** filter_function, double* infid) {
-    FFK_REQUIRE(result && gates && slots && gate_propagators && tau && offsets && index && omega && basis,
-                "NULL argument");
+    const GateTable g{gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                      hermitian_basis, d, A, N};
+    FFK_REQUIRE(result, "NULL argument");
     FFK_REQUIRE(total_propagators && filter_function, "NULL output argument");
     FFK_REQUIRE(ffk::sequences_supported(d, N, A), "unsupported shape d=%d N=%d A=%d (need d = 2, N = 4, 1 <= A <= 4)",
                 d, N, A);
-    FFK_REQUIRE(hermitian_basis != 0, "the batched rule needs a Hermitian basis");
-    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 1,
-                "empty or oversized axis: T=%d P=%d W=%d", T, P, W);
-    FFK_REQUIRE(offsets[0] == 0, "offsets[0] = %d, expected 0", offsets[0]);
-    for (int p = 0; p < P; ++p)
-        FFK_REQUIRE(offsets[p + 1] > offsets[p], "offsets not increasing at sequence %d (%d -> %d)", p, offsets[p],
-                    offsets[p + 1]);
-    const size_t n_index = size_t(offsets[P]);
-    for (size_t g = 0; g < n_index; ++g)
-        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
+    size_t n_index = 0;
+    if (int rc = check_gate_table(g, 1, &n_index)) return rc;
     if (spectrum) {
         if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d_infidelity, infid && W >= 2)) return rc;
     } else {
@@ -970,30 +959,14 @@ int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const
     // where each gate's control matrix lies on the device: in its own handle, or in the uploaded host table
     std::vector<const unsigned char*> tab;
     int n_host = 0;
-    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
-    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    if (int rc = locate_gates(g, dev, &tab, &n_host)) return rc;
     const SeqLayout L = seq_layout(T, P, n_index, n_host, d, A, N, W, sh, n_idx);
     if (int rc = ensure_blocks(result, dev, L.end, L.outputs_end)) return rc;
     unsigned char* hp = static_cast<unsigned char*>(result->pin.ptr);
     unsigned char* dp = static_cast<unsigned char*>(result->dev.ptr);
-    const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
+    const size_t dd = size_t(d)*d;
     PassClock clock;
-    // the sequences sorted by length, longest first (stable): the rule kernel deals them out in this order
-    std::vector<int32_t> order(P);
-    for (int p = 0; p < P; ++p) order[p] = p;
-    std::stable_sort(order.begin(), order.end(), [offsets](int32_t a, int32_t b) {
-        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
-    });
-    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
-    std::memcpy(hp + L.index, index, 4*n_index);
-    std::memcpy(hp + L.order, order.data(), 4*size_t(P));
-    std::memcpy(hp + L.tau, tau, 8*size_t(T));
-    std::memcpy(hp + L.omega, omega, 8*size_t(W));
-    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
-    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
-    place_host_rows(&tab, dp + L.host, row);
-    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
-    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    stage_gate_table(g, L.table, n_index, longest_first(offsets, P).data(), &tab, hp, dp);
     if (spectrum) stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp + L.S, hp + L.idx);
     hipStream_t s;
     if (int rc = resident_stream(&s)) return rc;
@@ -1001,21 +974,15 @@ int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const
     clock.lap();
     auto at = [dp](size_t off) { return dp + off; };
     FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
-    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
-    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.index));
+    const GateTableDevice D(dp, L.table);
     cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
     double* dL = reinterpret_cast<double*>(at(L.L));
     cplx* dF = reinterpret_cast<cplx*>(at(L.F));
-    FFK_HIP(ffk::launch_sequences_front(reinterpret_cast<const cplx*>(at(L.U)), reinterpret_cast<const double*>(at(L.tau)),
-                                        reinterpret_cast<const double*>(at(L.omega)), T, W, dOff, dIdx, P,
-                                        reinterpret_cast<const cplx*>(at(L.basis)), dPh, dL,
-                                        reinterpret_cast<cplx*>(at(L.Q)), s));
-    FFK_HIP(ffk::launch_sequences_rule(dPh, reinterpret_cast<const cplx* const*>(at(L.tab)), dL, dOff, dIdx,
-                                       reinterpret_cast<const int32_t*>(at(L.order)), P, T, A, W,
+    FFK_HIP(launch_gate_table_front(g, D, dPh, dL, reinterpret_cast<cplx*>(at(L.Q)), s));
+    FFK_HIP(ffk::launch_sequences_rule(dPh, D.tab, dL, D.offsets, D.index, D.order, P, T, A, W,
                                        reinterpret_cast<cplx*>(at(L.R)), dF, s));
     if (spectrum)
-        FFK_HIP(ffk::launch_infidelity_pulses(dF, A, W, P, reinterpret_cast<const cplx*>(at(L.S)), s_ndim,
-                                              reinterpret_cast<const double*>(at(L.omega)),
+        FFK_HIP(ffk::launch_infidelity_pulses(dF, A, W, P, reinterpret_cast<const cplx*>(at(L.S)), s_ndim, D.omega,
                                               reinterpret_cast<const int32_t*>(at(L.idx)), n_idx, d_infidelity,
                                               reinterpret_cast<double*>(at(L.infid)), s));
     FFK_HIP(hipMemcpyAsync(hp + L.Q, dp + L.Q, L.outputs_end - L.Q, hipMemcpyDeviceToHost, s));
@@ -1027,7 +994,7 @@ int ffk_concatenate_sequences_resident(ffk_resident* result, ffk_resident* const
     std::memcpy(total_propagators, hp + L.Q, 16*size_t(P)*dd);
     *filter_function = reinterpret_cast<double*>(hp + L.F);
     if (spectrum) std::memcpy(infid, hp + L.infid, 8*size_t(P)*sh.n_out);
-    result->hold(ffk_resident::MEMBERS, P, d, W, N, A, L.R, L.F, L.omega);
+    result->hold(ffk_resident::MEMBERS, P, d, W, N, A, L.R, L.F, L.table.omega);
     return FFK_OK;
 }
 
@@ -1093,8 +1060,10 @@ int ffk_resident_batch_infidelity(ffk_resident* r, const int32_t* members, int n
 //      (ff.correlation_infidelities; correlations.hip) ------------------------------------------------------------
 namespace {
 
+// (the table's `order` holds the sequences sorted by length class)
 struct CorrLayout {
-    size_t offsets, index, out_offsets, members, tau, omega, basis, U, tab, host, S, idx, inputs_end;   // one H2D
+    GateTableLayout table;
+    size_t out_offsets, S, idx, inputs_end;                                                             // one H2D
     size_t infid, outputs_end;                                                                          // one D2H
     size_t Q, phases, L, Qc, scale, part, end;                                                          // device only
 };
@@ -1106,16 +1075,8 @@ CorrLayout corr_layout(int T, int P, size_t n_index, int n_host, int d, int A, i
     const size_t dd = size_t(d)*d;
     size_t o = 0;
     auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
-    L.offsets = put(4*(size_t(P) + 1));
-    L.index = put(4*n_index);
+    L.table = gate_table_layout(put, T, P, n_index, n_host, d, A, N, W);
     L.out_offsets = put(8*(size_t(P) + 1));
-    L.members = put(4*size_t(P));
-    L.tau = put(8*size_t(T));
-    L.omega = put(8*size_t(W));
-    L.basis = put(16*size_t(N)*dd);
-    L.U = put(16*size_t(T)*dd);
-    L.tab = put(8*size_t(T));
-    L.host = put(16*size_t(A)*N*W*size_t(n_host));
     L.S = put(16*sh.rows*W);
     L.idx = put(4*size_t(n_idx));
     L.inputs_end = o;
@@ -1154,8 +1115,9 @@ int correlation_pass(bool two_qubit, ffk_resident* const* gates, const int32_t* 
                      int hermitian_basis, int d, int A, int N, const double* spectrum, int s_ndim,
                      int spectrum_is_real, const int32_t* idx, int n_idx, int d_infidelity,
                      const int64_t* out_offsets, double* infidelity) {
-    FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis && spectrum && idx &&
-                out_offsets && infidelity, "NULL argument");
+    const GateTable g{gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                      hermitian_basis, d, A, N};
+    FFK_REQUIRE(spectrum && idx && out_offsets && infidelity, "NULL argument");
     if (two_qubit)
         FFK_REQUIRE(ffk::sequences4_supported(d, N, A),
                     "unsupported shape d=%d N=%d A=%d (need d = 4, N = 16, 1 <= A <= 4)", d, N, A);
@@ -1164,22 +1126,20 @@ int correlation_pass(bool two_qubit, ffk_resident* const* gates, const int32_t* 
                     d, N, A);
     FFK_REQUIRE(hermitian_basis != 0, "the batched pass needs a Hermitian basis");
     FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
-    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 1,
-                "empty or oversized axis: T=%d P=%d W=%d", T, P, W);
+    size_t n_index = 0;
+    if (int rc = check_gate_table(g, 1, &n_index)) return rc;
     if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d_infidelity, W >= 2)) return rc;
     const int max_length = ffk::correlation_max_length();
-    FFK_REQUIRE(offsets[0] == 0 && out_offsets[0] == 0, "offsets[0] = %d, out_offsets[0] = %lld, expected 0",
-                offsets[0], static_cast<long long>(out_offsets[0]));
+    FFK_REQUIRE(out_offsets[0] == 0, "offsets[0] = %d, out_offsets[0] = %lld, expected 0", offsets[0],
+                static_cast<long long>(out_offsets[0]));
     for (int p = 0; p < P; ++p) {
         const int64_t G = int64_t(offsets[p + 1]) - offsets[p];
-        FFK_REQUIRE(G >= 1 && G <= max_length, "sequence %d has %lld positions, need 1 ... %d", p,
-                    static_cast<long long>(G), max_length);
+        FFK_REQUIRE(G <= max_length, "sequence %d has %lld positions, need 1 ... %d", p, static_cast<long long>(G),
+                    max_length);
         FFK_REQUIRE(out_offsets[p + 1] - out_offsets[p] == G*G, "out_offsets is not the prefix sum of G^2 at sequence %d",
                     p);
     }
-    const size_t n_index = size_t(offsets[P]), total = size_t(out_offsets[P]);
-    for (size_t g = 0; g < n_index; ++g)
-        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
+    const size_t total = size_t(out_offsets[P]);
     if (s_ndim <= 2 && !spectrum_is_real)
         for (size_t i = 0; i < spectrum_shape(s_ndim, n_idx).rows*W; ++i)
             FFK_REQUIRE(spectrum[2*i + 1] == 0.0, "the spectrum has an imaginary part at element %zu", i);
@@ -1188,10 +1148,8 @@ int correlation_pass(bool two_qubit, ffk_resident* const* gates, const int32_t* 
     FFK_HIP(hipGetDevice(&dev));
     std::vector<const unsigned char*> tab;
     int n_host = 0;
-    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
-    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    if (int rc = locate_gates(g, dev, &tab, &n_host)) return rc;
     const CorrLayout L = corr_layout(T, P, n_index, n_host, d, A, N, W, sh, n_idx, total);
-    const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
     // the sequences sorted by the length class whose kernel serves them (stable), and how many of each
     std::vector<int32_t> members(P);
     int class_counts[4] = {0, 0, 0, 0};
@@ -1211,53 +1169,34 @@ int correlation_pass(bool two_qubit, ffk_resident* const* gates, const int32_t* 
     void* base = nullptr;
     if (int rc = arena_reserve(L.end, &base)) return rc;
     unsigned char* dp = static_cast<unsigned char*>(base);
-    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
-    std::memcpy(hp + L.index, index, 4*n_index);
+    stage_gate_table(g, L.table, n_index, members.data(), &tab, hp, dp);
     std::memcpy(hp + L.out_offsets, out_offsets, 8*(size_t(P) + 1));
-    std::memcpy(hp + L.members, members.data(), 4*size_t(P));
-    std::memcpy(hp + L.tau, tau, 8*size_t(T));
-    std::memcpy(hp + L.omega, omega, 8*size_t(W));
-    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
-    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
-    place_host_rows(&tab, dp + L.host, row);
-    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
-    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
     stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp + L.S, hp + L.idx);
     StreamDrain drain{s};
     auto at = [dp](size_t off) { return dp + off; };
     FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
-    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
-    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.index));
+    const GateTableDevice D(dp, L.table);
     const int64_t* dOut = reinterpret_cast<const int64_t*>(at(L.out_offsets));
-    const double* dOmega = reinterpret_cast<const double*>(at(L.omega));
     cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
     double* dL = reinterpret_cast<double*>(at(L.L));
     double* dQc = reinterpret_cast<double*>(at(L.Qc));
     cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
     double* dPart = reinterpret_cast<double*>(at(L.part));
-    const cplx* dU = reinterpret_cast<const cplx*>(at(L.U));
-    const double* dTau = reinterpret_cast<const double*>(at(L.tau));
-    const cplx* dBasis = reinterpret_cast<const cplx*>(at(L.basis));
-    const cplx* const* dTab = reinterpret_cast<const cplx* const*>(at(L.tab));
-    const int32_t* dMembers = reinterpret_cast<const int32_t*>(at(L.members));
     const int32_t* dSel = reinterpret_cast<const int32_t*>(at(L.idx));
-    cplx* dQ = reinterpret_cast<cplx*>(at(L.Q));
-    if (two_qubit) {
-        FFK_HIP(ffk::launch_sequences4_front(dU, dTau, dOmega, T, W, dOff, dIdx, P, dBasis, dPh, dL, dQ, s));
-        FFK_HIP(ffk::launch_correlations4_prefix(dL, dOff, dIdx, P, dQc, s));
-    } else {
-        FFK_HIP(ffk::launch_sequences_front(dU, dTau, dOmega, T, W, dOff, dIdx, P, dBasis, dPh, dL, dQ, s));
-        FFK_HIP(ffk::launch_correlation_prefix(dL, dOff, dIdx, P, dQc, s));
-    }
-    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(sh.rows), W, dOmega, W, 0, dScale,
+    FFK_HIP(launch_gate_table_front(g, D, dPh, dL, reinterpret_cast<cplx*>(at(L.Q)), s));
+    if (two_qubit)
+        FFK_HIP(ffk::launch_correlations4_prefix(dL, D.offsets, D.index, P, dQc, s));
+    else
+        FFK_HIP(ffk::launch_correlation_prefix(dL, D.offsets, D.index, P, dQc, s));
+    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(sh.rows), W, D.omega, W, 0, dScale,
                                          s));
     if (two_qubit)
-        FFK_HIP(ffk::launch_correlations4_gram(dPh, dTab, dQc, dOff, dIdx, dOut, dMembers, class_counts, W, dScale,
-                                               s_ndim, dSel, n_idx, d_infidelity, int64_t(total), dPart, s));
+        FFK_HIP(ffk::launch_correlations4_gram(dPh, D.tab, dQc, D.offsets, D.index, dOut, D.order, class_counts, W,
+                                               dScale, s_ndim, dSel, n_idx, d_infidelity, int64_t(total), dPart, s));
     else
-        FFK_HIP(ffk::launch_correlation_gram(dPh, dTab, dQc, dOff, dIdx, dOut, dMembers, class_counts, W, dScale,
-                                             s_ndim, dSel, n_idx, d_infidelity, int64_t(total), dPart, s));
-    FFK_HIP(ffk::launch_correlation_reduce(dPart, dOut, dOff, P, n_idx, W, int64_t(total),
+        FFK_HIP(ffk::launch_correlation_gram(dPh, D.tab, dQc, D.offsets, D.index, dOut, D.order, class_counts, W,
+                                             dScale, s_ndim, dSel, n_idx, d_infidelity, int64_t(total), dPart, s));
+    FFK_HIP(ffk::launch_correlation_reduce(dPart, dOut, D.offsets, P, n_idx, W, int64_t(total),
                                            reinterpret_cast<double*>(at(L.infid)), s));
     FFK_HIP(hipMemcpyAsync(hp + L.infid, dp + L.infid, 8*total*n_idx, hipMemcpyDeviceToHost, s));
     FFK_HIP(hipStreamSynchronize(s));
@@ -1307,7 +1246,8 @@ int ffk_sequence_correlation_infidelities4(ffk_resident* const* gates, const int
 namespace {
 
 struct SeqInfidLayout {
-    size_t offsets, index, order, tau, omega, basis, U, tab, host, S, idx, inputs_end;    // one H2D
+    GateTableLayout table;
+    size_t S, idx, inputs_end;                                                            // one H2D
     size_t infid, Q, small_outputs_end, F, outputs_end;                                   // one D2H (F if asked for)
     size_t phases, L, end;                                                                // device only
 };
@@ -1318,15 +1258,7 @@ SeqInfidLayout seq_infid_layout(int T, int P, size_t n_index, int n_host, int d,
     const size_t dd = size_t(d)*d;
     size_t o = 0;
     auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
-    L.offsets = put(4*(size_t(P) + 1));
-    L.index = put(4*n_index);
-    L.order = put(4*size_t(P));
-    L.tau = put(8*size_t(T));
-    L.omega = put(8*size_t(W));
-    L.basis = put(16*size_t(N)*dd);
-    L.U = put(16*size_t(T)*dd);
-    L.tab = put(8*size_t(T));
-    L.host = put(16*size_t(A)*N*W*size_t(n_host));
+    L.table = gate_table_layout(put, T, P, n_index, n_host, d, A, N, W);
     L.S = put(16*sh.rows*W);
     L.idx = put(4*size_t(n_idx));
     L.inputs_end = o;
@@ -1362,21 +1294,14 @@ int ffk_sequence_infidelities(ffk_resident* const* gates, const int32_t* slots, 
                               int hermitian_basis, int d, int A, int N, const double* spectrum, int s_ndim,
                               int spectrum_is_real, const int32_t* idx, int n_idx, int d_infidelity,
                               double* infidelity, double* total_propagators, double* filter_function) {
-    FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis, "NULL argument");
+    const GateTable g{gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                      hermitian_basis, d, A, N};
     FFK_REQUIRE(spectrum ? infidelity != nullptr : (total_propagators || filter_function),
                 "NULL output argument: a spectrum needs infidelity, no spectrum another output");
     FFK_REQUIRE(ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A),
                 "unsupported shape d=%d N=%d A=%d (need (d, N) = (2, 4) or (4, 16), 1 <= A <= 4)", d, N, A);
-    FFK_REQUIRE(hermitian_basis != 0, "the batched rule needs a Hermitian basis");
-    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 1,
-                "empty or oversized axis: T=%d P=%d W=%d", T, P, W);
-    FFK_REQUIRE(offsets[0] == 0, "offsets[0] = %d, expected 0", offsets[0]);
-    for (int p = 0; p < P; ++p)
-        FFK_REQUIRE(offsets[p + 1] > offsets[p], "offsets not increasing at sequence %d (%d -> %d)", p, offsets[p],
-                    offsets[p + 1]);
-    const size_t n_index = size_t(offsets[P]);
-    for (size_t g = 0; g < n_index; ++g)
-        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
+    size_t n_index = 0;
+    if (int rc = check_gate_table(g, 1, &n_index)) return rc;
     if (spectrum) {
         if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d_infidelity, W >= 2)) return rc;
         FFK_REQUIRE(P <= 65535, "the integral takes at most 65535 sequences per pass, got %d", P);
@@ -1388,17 +1313,10 @@ int ffk_sequence_infidelities(ffk_resident* const* gates, const int32_t* slots, 
     FFK_HIP(hipGetDevice(&dev));
     std::vector<const unsigned char*> tab;
     int n_host = 0;
-    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
-    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    if (int rc = locate_gates(g, dev, &tab, &n_host)) return rc;
     const SeqInfidLayout L = seq_infid_layout(T, P, n_index, n_host, d, A, N, W, sh, n_idx);
-    const size_t dd = size_t(d)*d, row = 16*size_t(A)*N*W;
+    const size_t dd = size_t(d)*d;
     const size_t copied_end = filter_function ? L.outputs_end : L.small_outputs_end;
-    // the sequences sorted by length, longest first (stable): the rule kernels deal them out in this order
-    std::vector<int32_t> order(P);
-    for (int p = 0; p < P; ++p) order[p] = p;
-    std::stable_sort(order.begin(), order.end(), [offsets](int32_t a, int32_t b) {
-        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
-    });
     PinLease pin;
     if (int rc = pin.take(copied_end, dev)) return rc;
     unsigned char* hp = pin.ptr();
@@ -1408,41 +1326,22 @@ int ffk_sequence_infidelities(ffk_resident* const* gates, const int32_t* slots, 
     void* base = nullptr;
     if (int rc = arena_reserve(L.end, &base)) return rc;
     unsigned char* dp = static_cast<unsigned char*>(base);
-    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
-    std::memcpy(hp + L.index, index, 4*n_index);
-    std::memcpy(hp + L.order, order.data(), 4*size_t(P));
-    std::memcpy(hp + L.tau, tau, 8*size_t(T));
-    std::memcpy(hp + L.omega, omega, 8*size_t(W));
-    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
-    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
-    place_host_rows(&tab, dp + L.host, row);
-    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
-    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    stage_gate_table(g, L.table, n_index, longest_first(offsets, P).data(), &tab, hp, dp);
     if (spectrum) stage_spectrum(spectrum, spectrum_is_real != 0, sh.rows*W, idx, n_idx, hp + L.S, hp + L.idx);
     StreamDrain drain{s};
     auto at = [dp](size_t off) { return dp + off; };
     FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
-    const cplx* dU = reinterpret_cast<const cplx*>(at(L.U));
-    const double* dTau = reinterpret_cast<const double*>(at(L.tau));
-    const double* dOmega = reinterpret_cast<const double*>(at(L.omega));
-    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
-    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.index));
-    const int32_t* dOrder = reinterpret_cast<const int32_t*>(at(L.order));
-    const cplx* dBasis = reinterpret_cast<const cplx*>(at(L.basis));
-    const cplx* const* dTab = reinterpret_cast<const cplx* const*>(at(L.tab));
+    const GateTableDevice D(dp, L.table);
     cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
     double* dL = reinterpret_cast<double*>(at(L.L));
-    cplx* dQ = reinterpret_cast<cplx*>(at(L.Q));
     cplx* dF = reinterpret_cast<cplx*>(at(L.F));
-    if (d == 2) {
-        FFK_HIP(ffk::launch_sequences_front(dU, dTau, dOmega, T, W, dOff, dIdx, P, dBasis, dPh, dL, dQ, s));
-        FFK_HIP(ffk::launch_sequences_rule(dPh, dTab, dL, dOff, dIdx, dOrder, P, T, A, W, nullptr, dF, s));
-    } else {
-        FFK_HIP(ffk::launch_sequences4_front(dU, dTau, dOmega, T, W, dOff, dIdx, P, dBasis, dPh, dL, dQ, s));
-        FFK_HIP(ffk::launch_sequences4_rule(dPh, dTab, dL, dOff, dIdx, dOrder, P, T, A, W, dF, s));
-    }
+    FFK_HIP(launch_gate_table_front(g, D, dPh, dL, reinterpret_cast<cplx*>(at(L.Q)), s));
+    if (d == 2)
+        FFK_HIP(ffk::launch_sequences_rule(dPh, D.tab, dL, D.offsets, D.index, D.order, P, T, A, W, nullptr, dF, s));
+    else
+        FFK_HIP(ffk::launch_sequences4_rule(dPh, D.tab, dL, D.offsets, D.index, D.order, P, T, A, W, dF, s));
     if (spectrum)
-        FFK_HIP(ffk::launch_infidelity_pulses(dF, A, W, P, reinterpret_cast<const cplx*>(at(L.S)), s_ndim, dOmega,
+        FFK_HIP(ffk::launch_infidelity_pulses(dF, A, W, P, reinterpret_cast<const cplx*>(at(L.S)), s_ndim, D.omega,
                                               reinterpret_cast<const int32_t*>(at(L.idx)), n_idx, d_infidelity,
                                               reinterpret_cast<double*>(at(L.infid)), s));
     FFK_HIP(hipMemcpyAsync(hp + L.infid, dp + L.infid, copied_end - L.infid, hipMemcpyDeviceToHost, s));
@@ -1599,7 +1498,8 @@ int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slo
 namespace {
 
 struct SeqProcLayout {
-    size_t offsets, index, order, tau, omega, basis, U, tab, host, S, idx, inputs_end;    // one H2D
+    GateTableLayout table;
+    size_t S, idx, inputs_end;                                                            // one H2D
     size_t out, flags, Q, outputs_end;                                                    // one D2H
     size_t phases, L, scale, partial, gamma, K, cumulant, end;                            // device only
 };
@@ -1614,15 +1514,7 @@ SeqProcLayout seq_proc_layout(int T, int P, size_t n_index, int n_host, int d, i
     const int width = ffk::sequence_processes_block_width(d, A);
     size_t o = 0;
     auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
-    L.offsets = put(4*(size_t(P) + 1));
-    L.index = put(4*n_index);
-    L.order = put(4*size_t(P));
-    L.tau = put(8*size_t(T));
-    L.omega = put(8*size_t(W));
-    L.basis = put(16*size_t(N)*dd);
-    L.U = put(16*size_t(T)*dd);
-    L.tab = put(8*size_t(T));
-    L.host = put(16*size_t(A)*N*W*size_t(n_host));
+    L.table = gate_table_layout(put, T, P, n_index, n_host, d, A, N, W);
     L.S = put(16*rows*W);
     L.idx = put(4*size_t(n_idx));
     L.inputs_end = o;
@@ -1662,26 +1554,19 @@ int ffk_sequence_processes(ffk_resident* const* gates, const int32_t* slots, con
                            int hermitian_basis, int d, int A, int N, int single_qubit, const double* spectrum,
                            int s_ndim, int n_spectra, const int32_t* idx, int n_idx, int stage, double* out,
                            int32_t* not_finite, double* total_propagators) {
-    FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis && spectrum && idx &&
-                out && not_finite, "NULL argument");
+    const GateTable g{gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                      hermitian_basis, d, A, N};
+    FFK_REQUIRE(spectrum && idx && out && not_finite, "NULL argument");
     FFK_REQUIRE(ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A),
                 "unsupported shape d=%d N=%d A=%d (need (d, N) = (2, 4) or (4, 16), 1 <= A <= 4)", d, N, A);
-    FFK_REQUIRE(hermitian_basis != 0, "the batched rule needs a Hermitian basis");
     FFK_REQUIRE(!single_qubit || d == 2, "single-qubit expression needs d = 2, N = 4");
-    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 2,
-                "empty or oversized axis: T=%d P=%d W=%d (need W >= 2)", T, P, W);
+    size_t n_index = 0;
+    if (int rc = check_gate_table(g, 2, &n_index)) return rc;
     FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
     FFK_REQUIRE(n_spectra >= 1 && n_spectra <= 65535, "n_spectra = %d, need 1 ... 65535", n_spectra);
     FFK_REQUIRE(stage >= 1 && stage <= 3, "stage = %d, need 1 (decay amplitudes), 2 (cumulant function) or 3 (error "
                 "transfer matrix)", stage);
     if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d, true)) return rc;
-    FFK_REQUIRE(offsets[0] == 0, "offsets[0] = %d, expected 0", offsets[0]);
-    for (int p = 0; p < P; ++p)
-        FFK_REQUIRE(offsets[p + 1] > offsets[p], "offsets not increasing at sequence %d (%d -> %d)", p, offsets[p],
-                    offsets[p + 1]);
-    const size_t n_index = size_t(offsets[P]);
-    for (size_t g = 0; g < n_index; ++g)
-        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
     const size_t tiles = size_t(n_spectra)*P*n_idx, members = size_t(n_spectra)*P;
     FFK_REQUIRE(tiles <= (size_t(1) << 26), "%zu decay-amplitude tiles exceed one pass", tiles);
     FFK_REQUIRE(stage < 2 || single_qubit || tiles <= 65535,
@@ -1692,18 +1577,11 @@ int ffk_sequence_processes(ffk_resident* const* gates, const int32_t* slots, con
     FFK_HIP(hipGetDevice(&dev));
     std::vector<const unsigned char*> tab;
     int n_host = 0;
-    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
-    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    if (int rc = locate_gates(g, dev, &tab, &n_host)) return rc;
     const SeqProcLayout L = seq_proc_layout(T, P, n_index, n_host, d, A, N, W, n_idx, s_ndim, n_spectra, stage,
                                             single_qubit != 0);
-    const size_t dd = size_t(d)*d, nn = size_t(N)*N, row = 16*size_t(A)*N*W;
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N;
     const size_t out_bytes = stage == 3 ? 8*members*nn : 8*tiles*nn;
-    // the sequences sorted by length, longest first (stable): the kernels deal them out in this order
-    std::vector<int32_t> order(P);
-    for (int p = 0; p < P; ++p) order[p] = p;
-    std::stable_sort(order.begin(), order.end(), [offsets](int32_t a, int32_t b) {
-        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
-    });
     PinLease pin;
     if (int rc = pin.take(L.outputs_end, dev)) return rc;
     unsigned char* hp = pin.ptr();
@@ -1713,47 +1591,27 @@ int ffk_sequence_processes(ffk_resident* const* gates, const int32_t* slots, con
     void* base = nullptr;
     if (int rc = arena_reserve(L.end, &base)) return rc;
     unsigned char* dp = static_cast<unsigned char*>(base);
-    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
-    std::memcpy(hp + L.index, index, 4*n_index);
-    std::memcpy(hp + L.order, order.data(), 4*size_t(P));
-    std::memcpy(hp + L.tau, tau, 8*size_t(T));
-    std::memcpy(hp + L.omega, omega, 8*size_t(W));
-    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
-    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
-    place_host_rows(&tab, dp + L.host, row);
-    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
-    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    stage_gate_table(g, L.table, n_index, longest_first(offsets, P).data(), &tab, hp, dp);
     stage_spectrum(spectrum, true, s_rows*W, idx, n_idx, hp + L.S, hp + L.idx);
     StreamDrain drain{s};
     auto at = [dp](size_t off) { return dp + off; };
     FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
-    const cplx* dU = reinterpret_cast<const cplx*>(at(L.U));
-    const double* dTau = reinterpret_cast<const double*>(at(L.tau));
-    const double* dOmega = reinterpret_cast<const double*>(at(L.omega));
-    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
-    const int32_t* dIndex = reinterpret_cast<const int32_t*>(at(L.index));
-    const int32_t* dOrder = reinterpret_cast<const int32_t*>(at(L.order));
+    const GateTableDevice D(dp, L.table);
     const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.idx));
-    const cplx* dBasis = reinterpret_cast<const cplx*>(at(L.basis));
-    const cplx* const* dTab = reinterpret_cast<const cplx* const*>(at(L.tab));
     cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
     double* dL = reinterpret_cast<double*>(at(L.L));
-    cplx* dQ = reinterpret_cast<cplx*>(at(L.Q));
     cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
     double* dGamma = reinterpret_cast<double*>(at(L.gamma));
     double* dK = reinterpret_cast<double*>(at(L.K));
     int32_t* dFlags = reinterpret_cast<int32_t*>(at(L.flags));
     FFK_HIP(hipMemsetAsync(dFlags, 0, 4*members, s));
-    if (d == 2)
-        FFK_HIP(ffk::launch_sequences_front(dU, dTau, dOmega, T, W, dOff, dIndex, P, dBasis, dPh, dL, dQ, s));
-    else
-        FFK_HIP(ffk::launch_sequences4_front(dU, dTau, dOmega, T, W, dOff, dIndex, P, dBasis, dPh, dL, dQ, s));
-    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(s_rows), W, dOmega, W, 0, dScale,
+    FFK_HIP(launch_gate_table_front(g, D, dPh, dL, reinterpret_cast<cplx*>(at(L.Q)), s));
+    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(s_rows), W, D.omega, W, 0, dScale,
                                          s));
-    FFK_HIP(ffk::launch_sequences_gamma(d, dPh, dTab, dL, dOff, dIndex, dOrder, P, T, A, W, dScale, s_ndim, n_spectra,
-                                        dIdx, n_idx, reinterpret_cast<double*>(at(L.partial)), dGamma, s));
+    FFK_HIP(ffk::launch_sequences_gamma(d, dPh, D.tab, dL, D.offsets, D.index, D.order, P, T, A, W, dScale, s_ndim,
+                                        n_spectra, dIdx, n_idx, reinterpret_cast<double*>(at(L.partial)), dGamma, s));
     if (stage >= 2)
-        FFK_HIP(ffk::launch_cumulant_function(dGamma, tiles, N, d, dBasis, single_qubit, dK, at(L.cumulant), s));
+        FFK_HIP(ffk::launch_cumulant_function(dGamma, tiles, N, d, D.basis, single_qubit, dK, at(L.cumulant), s));
     if (stage >= 3)
         FFK_HIP(ffk::launch_processes_expm(dK, int(members), n_idx, N, reinterpret_cast<double*>(at(L.out)), dFlags,
                                            s));
@@ -1771,7 +1629,8 @@ int ffk_sequence_processes(ffk_resident* const* gates, const int32_t* slots, con
 namespace {
 
 struct SeqShiftLayout {
-    size_t offsets, index, order, tau, omega, basis, U, tab, host, S, idx, shifts, inputs_end;    // one H2D
+    GateTableLayout table;
+    size_t S, idx, shifts, inputs_end;                                                            // one H2D
     size_t out, Q, outputs_end;                                                                   // one D2H
     size_t phases, L, scale, partial, end;                                                        // device only
 };
@@ -1785,15 +1644,7 @@ SeqShiftLayout seq_shift_layout(int T, int P, size_t n_index, int n_host, int d,
     const int width = ffk::sequence_second_order_block_width(d, A);
     size_t o = 0;
     auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
-    L.offsets = put(4*(size_t(P) + 1));
-    L.index = put(4*n_index);
-    L.order = put(4*size_t(P));
-    L.tau = put(8*size_t(T));
-    L.omega = put(8*size_t(W));
-    L.basis = put(16*size_t(N)*dd);
-    L.U = put(16*size_t(T)*dd);
-    L.tab = put(8*size_t(T));
-    L.host = put(16*size_t(A)*N*W*size_t(n_host));
+    L.table = gate_table_layout(put, T, P, n_index, n_host, d, A, N, W);
     L.S = put(16*rows*W);
     L.idx = put(4*size_t(n_idx));
     L.shifts = put(8*size_t(n_spectra)*T*n_idx*nn);
@@ -1829,13 +1680,13 @@ int ffk_sequence_frequency_shifts(ffk_resident* const* gates, const int32_t* slo
                                   int hermitian_basis, int d, int A, int N, const double* spectrum, int s_ndim,
                                   int n_spectra, const int32_t* idx, int n_idx, const double* gate_shifts, double* out,
                                   int32_t* not_finite, double* total_propagators) {
-    FFK_REQUIRE(gates && slots && gate_propagators && tau && offsets && index && omega && basis && spectrum && idx &&
-                gate_shifts && out && not_finite, "NULL argument");
+    const GateTable g{gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                      hermitian_basis, d, A, N};
+    FFK_REQUIRE(spectrum && idx && gate_shifts && out && not_finite, "NULL argument");
     FFK_REQUIRE(ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A),
                 "unsupported shape d=%d N=%d A=%d (need (d, N) = (2, 4) or (4, 16), 1 <= A <= 4)", d, N, A);
-    FFK_REQUIRE(hermitian_basis != 0, "the batched rule needs a Hermitian basis");
-    FFK_REQUIRE(T >= 1 && T <= (1 << 20) && P >= 1 && P <= (1 << 24) && W >= 2,
-                "empty or oversized axis: T=%d P=%d W=%d (need W >= 2)", T, P, W);
+    size_t n_index = 0;
+    if (int rc = check_gate_table(g, 2, &n_index)) return rc;
     FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
     FFK_REQUIRE(n_spectra >= 1 && n_spectra <= 65535, "n_spectra = %d, need 1 ... 65535", n_spectra);
     if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d, true)) return rc;
@@ -1843,13 +1694,6 @@ int ffk_sequence_frequency_shifts(ffk_resident* const* gates, const int32_t* slo
         for (int m = 0; m < i; ++m)
             FFK_REQUIRE(idx[i] != idx[m], "idx[%d] = idx[%d] = %d: the selected operators must be distinct", m, i,
                         idx[i]);
-    FFK_REQUIRE(offsets[0] == 0, "offsets[0] = %d, expected 0", offsets[0]);
-    for (int p = 0; p < P; ++p)
-        FFK_REQUIRE(offsets[p + 1] > offsets[p], "offsets not increasing at sequence %d (%d -> %d)", p, offsets[p],
-                    offsets[p + 1]);
-    const size_t n_index = size_t(offsets[P]);
-    for (size_t g = 0; g < n_index; ++g)
-        FFK_REQUIRE(index[g] >= 0 && index[g] < T, "index[%zu] = %d outside [0, %d)", g, index[g], T);
     const size_t tiles = size_t(n_spectra)*P*n_idx, members = size_t(n_spectra)*P;
     FFK_REQUIRE(tiles <= (size_t(1) << 26), "%zu tiles exceed one pass", tiles);
     const size_t s_rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
@@ -1857,16 +1701,9 @@ int ffk_sequence_frequency_shifts(ffk_resident* const* gates, const int32_t* slo
     FFK_HIP(hipGetDevice(&dev));
     std::vector<const unsigned char*> tab;
     int n_host = 0;
-    if (int rc = locate_control_matrices(gates, slots, T, dev, d, A, N, W, "gate", &tab, &n_host)) return rc;
-    FFK_REQUIRE(n_host == 0 || gate_table, "gate_table is NULL but %d gate(s) have no handle", n_host);
+    if (int rc = locate_gates(g, dev, &tab, &n_host)) return rc;
     const SeqShiftLayout L = seq_shift_layout(T, P, n_index, n_host, d, A, N, W, n_idx, s_ndim, n_spectra);
-    const size_t dd = size_t(d)*d, nn = size_t(N)*N, row = 16*size_t(A)*N*W;
-    // the sequences sorted by length, longest first (stable): the kernels deal them out in this order
-    std::vector<int32_t> order(P);
-    for (int p = 0; p < P; ++p) order[p] = p;
-    std::stable_sort(order.begin(), order.end(), [offsets](int32_t a, int32_t b) {
-        return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b];
-    });
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N;
     PinLease pin;
     if (int rc = pin.take(L.outputs_end, dev)) return rc;
     unsigned char* hp = pin.ptr();
@@ -1876,41 +1713,21 @@ int ffk_sequence_frequency_shifts(ffk_resident* const* gates, const int32_t* slo
     void* base = nullptr;
     if (int rc = arena_reserve(L.end, &base)) return rc;
     unsigned char* dp = static_cast<unsigned char*>(base);
-    std::memcpy(hp + L.offsets, offsets, 4*(size_t(P) + 1));
-    std::memcpy(hp + L.index, index, 4*n_index);
-    std::memcpy(hp + L.order, order.data(), 4*size_t(P));
-    std::memcpy(hp + L.tau, tau, 8*size_t(T));
-    std::memcpy(hp + L.omega, omega, 8*size_t(W));
-    std::memcpy(hp + L.basis, basis, 16*size_t(N)*dd);
-    std::memcpy(hp + L.U, gate_propagators, 16*size_t(T)*dd);
-    place_host_rows(&tab, dp + L.host, row);
-    std::memcpy(hp + L.tab, tab.data(), 8*size_t(T));
-    if (n_host) std::memcpy(hp + L.host, gate_table, row*size_t(n_host));
+    stage_gate_table(g, L.table, n_index, longest_first(offsets, P).data(), &tab, hp, dp);
     stage_spectrum(spectrum, true, s_rows*W, idx, n_idx, hp + L.S, hp + L.idx);
     std::memcpy(hp + L.shifts, gate_shifts, 8*size_t(n_spectra)*T*n_idx*nn);
     StreamDrain drain{s};
     auto at = [dp](size_t off) { return dp + off; };
     FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
-    const cplx* dU = reinterpret_cast<const cplx*>(at(L.U));
-    const double* dTau = reinterpret_cast<const double*>(at(L.tau));
-    const double* dOmega = reinterpret_cast<const double*>(at(L.omega));
-    const int32_t* dOff = reinterpret_cast<const int32_t*>(at(L.offsets));
-    const int32_t* dIndex = reinterpret_cast<const int32_t*>(at(L.index));
-    const int32_t* dOrder = reinterpret_cast<const int32_t*>(at(L.order));
+    const GateTableDevice D(dp, L.table);
     const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.idx));
-    const cplx* dBasis = reinterpret_cast<const cplx*>(at(L.basis));
-    const cplx* const* dTab = reinterpret_cast<const cplx* const*>(at(L.tab));
     cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
     double* dL = reinterpret_cast<double*>(at(L.L));
-    cplx* dQ = reinterpret_cast<cplx*>(at(L.Q));
     cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
-    if (d == 2)
-        FFK_HIP(ffk::launch_sequences_front(dU, dTau, dOmega, T, W, dOff, dIndex, P, dBasis, dPh, dL, dQ, s));
-    else
-        FFK_HIP(ffk::launch_sequences4_front(dU, dTau, dOmega, T, W, dOff, dIndex, P, dBasis, dPh, dL, dQ, s));
-    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(s_rows), W, dOmega, W, 0, dScale,
+    FFK_HIP(launch_gate_table_front(g, D, dPh, dL, reinterpret_cast<cplx*>(at(L.Q)), s));
+    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(s_rows), W, D.omega, W, 0, dScale,
                                          s));
-    FFK_HIP(ffk::launch_sequence_second_order(d, dPh, dTab, dL, dOff, dIndex, dOrder, P, T, A, W, dScale, s_ndim,
+    FFK_HIP(ffk::launch_sequence_second_order(d, dPh, D.tab, dL, D.offsets, D.index, D.order, P, T, A, W, dScale, s_ndim,
                                               n_spectra, dIdx, n_idx, reinterpret_cast<const double*>(at(L.shifts)),
                                               reinterpret_cast<double*>(at(L.partial)),
                                               reinterpret_cast<double*>(at(L.out)), s));
@@ -2129,7 +1946,24 @@ extern "C" int ffk_selftest_host(int rounds, unsigned seed, char* report, int re
                 if (!ascending(HL) || HL.partial + 8*size_t((W + 63)/64)*ks*P*si*16 > HL.end ||
                     HL.end != ffk_sequence_frequency_shifts_workspace_bytes(T, P, n_index, n_host, 2, As, 4, W, si, sn, ks))
                     return -17;
+                // the process pass of the sequences, two-qubit gates: any stage, the cumulant workspace last (below stage
+                // 3 the requested array IS `out`, so gamma or K names an earlier offset a second time)
+                const int stage = pick(1, 3);
+                const size_t tiles = size_t(ks)*P*si;
+                const SeqProcLayout QL = seq_proc_layout(T, P, size_t(n_index), n_host, 4, As, 16, W, si, sn, ks, stage,
+                                                         false);
+                if ((stage == 3 && !ascending(QL)) || QL.inputs_end > QL.out || QL.outputs_end > QL.phases ||
+                    QL.cumulant + (stage >= 2 ? ffk::cumulant_workspace_bytes(tiles, 16, 4) : 0) > QL.end ||
+                    QL.end != ffk_sequence_processes_workspace_bytes(T, P, n_index, n_host, 4, As, 16, W, si, sn, ks, stage))
+                    return -18;
             }
+            // the infidelity pass of the sequences, either dimension
+            const int di = pick(0, 1) ? 4 : 2;
+            const SeqInfidLayout IL = seq_infid_layout(T, P, size_t(n_index), n_host, di, As, di*di, W,
+                                                       spectrum_shape(s_ndim, si), si);
+            if (!ascending(IL) || IL.L + 8*size_t(T)*di*di*di*di > IL.end ||
+                IL.end != ffk_sequence_infidelities_workspace_bytes(T, P, n_index, n_host, di, As, di*di, W, si, s_ndim))
+                return -19;
             const int Np = N < 16 ? N : 16, hosts = pick(0, P);
             const ProcLayout PL = proc_layout(P, hosts, A, Np, W, d, n_idx, s_ndim, false, true, true, true);
             if (!ascending(PL) || PL.end != ffk_resident_batch_processes_workspace_bytes(P, hosts, A, Np, W, d, n_idx, s_ndim))

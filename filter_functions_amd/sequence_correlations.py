@@ -10,17 +10,15 @@ single-qubit (d = 2) or two-qubit (d = 4) gates -- runs in passes of one H2D cop
 number of sequences and one D2H copy.  Neither the summands of the concatenation rule nor the pulse-correlation
 filter function (G, G, A, A, W) exist anywhere.  Everything else runs the loop's expression.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib, util
-from ._lib import as_c128, as_f64, check
+from ._gate_table import PassTable, batched_plan, validated
+from ._lib import as_f64, check
 from ._resident import spectrum_arguments
 from .batch import MAX_PULSES, PASS_BYTES, split_passes
 from .correlations import MAX_LENGTH, output_offsets, slabs
-from .sequence_infidelities import _on_grid, eligibility, index_arrays
-from .sequences import pack_sequences, resident_source
+from .sequence_infidelities import eligibility, index_arrays  # noqa: F401
 
 __all__ = ['sequence_correlation_infidelities']
 
@@ -51,32 +49,17 @@ def _loop(table, index, spectrum, omega, n_oper_identifiers):
 
 def _run_pass(gates, indices, plan, omega, S, idx):
     """One pass over the sequences *indices* (int32 arrays into *gates*): the list of their (G, G, n_idx) arrays."""
-    d, N, A = plan['d'], plan['N'], plan['A']
-    W, P = len(omega), len(indices)
+    d = plan['d']
     lengths = [len(i) for i in indices]
-    if W < 2:
+    if len(omega) < 2:
         return [np.zeros((G, G, len(idx))) for G in lengths]
-    used = np.unique(np.concatenate(indices))
-    slot_of = np.full(len(gates), -1, dtype=np.int32)
-    slot_of[used] = np.arange(len(used), dtype=np.int32)
-    table_gates = [gates[k] for k in used]
-    sources = [resident_source(g, d, W, N, A) for g in table_gates]
-    host = [g for g, src in zip(table_gates, sources) if src is None]
-    table = as_c128(np.array([g.get_control_matrix(omega) for g in host])) if host else None
-    handles = (ctypes.c_void_p*len(table_gates))(*[None if src is None else src[0].value for src in sources])
-    slots = np.array([-1 if src is None else src[1] for src in sources], dtype=np.int32)
-    U = as_c128(np.array([g.total_propagator for g in table_gates]))
-    tau = np.array([g.tau for g in table_gates], dtype=np.float64)
-    offsets, index, _ = pack_sequences([slot_of[i] for i in indices])
+    table = PassTable(gates, indices, plan, omega)
     out_offsets = output_offsets(lengths)
     S, real, idx, _ = spectrum_arguments(S, idx)
-    basis = as_c128(np.asarray(plan['basis']))
     out = np.empty((int(out_offsets[-1]), len(idx)), dtype=np.float64)
     lib = _lib.load()
     entry = lib.ffk_sequence_correlation_infidelities if d == 2 else lib.ffk_sequence_correlation_infidelities4
-    check(entry(handles, slots.ctypes.data, None if table is None else table.ctypes.data, U.ctypes.data,
-                tau.ctypes.data, len(table_gates), offsets.ctypes.data, index.ctypes.data, P, omega.ctypes.data, W,
-                basis.ctypes.data, 1, d, A, N, S.ctypes.data, S.ndim, real, idx.ctypes.data, len(idx), d,
+    check(entry(*table.c_arguments(), S.ctypes.data, S.ndim, real, idx.ctypes.data, len(idx), d,
                 out_offsets.ctypes.data, out.ctypes.data))
     return [out[a:b].reshape(G, G, len(idx)) for a, b, G in zip(out_offsets[:-1], out_offsets[1:], lengths)]
 
@@ -125,24 +108,10 @@ def sequence_correlation_infidelities(gates, sequences, spectrum, omega, n_oper_
     Every other sequence -- one gate, more than 256 gates, cross-spectra (n_idx, n_idx, n_omega) --, and every
     sequence of an ineligible gate set, evaluates the loop's expression inside this call.
     """
-    from .pulse_sequence import PulseSequence
-    gates = list(gates)
-    for gate in gates:
-        if not isinstance(gate, PulseSequence):
-            raise TypeError('Can only concatenate PulseSequences!')
-    indices = index_arrays(sequences, len(gates))
-    if not indices:
-        raise ValueError('Need at least one sequence.')
+    gates, indices = validated(gates, sequences)
     table = np.empty(len(gates), dtype=object)
     table[:] = gates
-    plan = eligibility(gates)
-    if plan is not None:
-        missing = [g for g in gates if not _on_grid(g, omega)]
-        if missing:
-            from .batch import get_filter_functions
-            get_filter_functions(missing, omega)
-        if not all('total_propagator' in g._data for g in gates):
-            plan = None
+    plan = batched_plan(gates, omega)
     selected = None
     if plan is not None:
         grid = as_f64(omega)

@@ -10,74 +10,15 @@ it is checked once per call.  An eligible gate set -- single-qubit (d = 2) or tw
 :func:`eligibility` -- runs in passes of one H2D copy, three launches whatever the number of sequences and one D2H
 copy; the sequences' control matrices are never written to memory.  Every other gate set runs the loop's expression.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib, util
-from ._lib import as_c128, as_f64, check
+from ._gate_table import PassTable, _on_grid, batched_plan, eligibility, index_arrays, validated  # noqa: F401
+from ._lib import as_f64, check
 from ._resident import spectrum_arguments
 from .batch import MAX_PULSES, PASS_BYTES, split_passes
-from .sequences import MAX_NOISE_OPERATORS, pack_sequences, resident_source
 
 __all__ = ['sequence_infidelities']
-
-
-def index_arrays(sequences, n_gates):
-    """The sequences as int32 arrays in [0, n_gates), with the rules of ``np.asarray(gates, dtype=object)[s]``:
-    negative indices wrap, others out of range raise IndexError; an empty sequence raises ValueError, an index that
-    is no integer TypeError."""
-    out = []
-    for p, s in enumerate(sequences):
-        a = np.asarray(s)
-        if a.ndim != 1:
-            raise ValueError(f'Sequence {p}: expected a one-dimensional array of gate indices, not shape {a.shape}.')
-        if a.size == 0:
-            raise ValueError(f'Sequence {p} is empty.')
-        if a.dtype.kind not in 'iu':
-            raise TypeError(f'Sequence {p}: gate indices must be integers, not {a.dtype}.')
-        bad = (a < -n_gates) | (a >= n_gates)
-        if bad.any():
-            raise IndexError(f'Sequence {p}: index {a[bad][0]} is out of bounds for {n_gates} gates.')
-        out.append(np.where(a < 0, a + n_gates, a).astype(np.int32))
-    return out
-
-
-def eligibility(gates):
-    """What the batched route needs of the gate set, dict(d, N, A, basis), or None if the loop's expression is to run.
-
-    Eligible: all gates have d = 2 or all have d = 4; they share one basis (the same object, else equal arrays) that
-    is Hermitian, traceless and has d^2 elements; they carry identical noise-operator identifiers in identical order
-    with equal operator arrays, 1 to 4 of them, unique and in the sorted order ``ff.concatenate`` gives the new pulse
-    (so that row a of the result means the same operator as in the loop).  Whether every gate knows its total
-    propagator is checked by the caller, after the control matrices are complete."""
-    if not gates:
-        return None
-    first = gates[0]
-    d, basis = first.d, first.basis
-    if d not in (2, 4) or any(g.d != d or g.c_opers.shape[-1] != d for g in gates):
-        return None
-    if len(basis) != d*d or not basis.isherm or not basis.istraceless:
-        return None
-    reference = np.asarray(basis)
-    for g in gates[1:]:
-        if g.basis is not basis and not (np.shape(g.basis) == reference.shape
-                                         and np.array_equal(np.asarray(g.basis), reference)):
-            return None
-    names = [str(i) for i in first.n_oper_identifiers]
-    A = len(names)
-    if not 1 <= A <= MAX_NOISE_OPERATORS or names != sorted(set(names)):
-        return None
-    n_opers = np.asarray(first.n_opers)
-    for g in gates[1:]:
-        if [str(i) for i in g.n_oper_identifiers] != names or not np.array_equal(np.asarray(g.n_opers), n_opers):
-            return None
-    return dict(d=d, N=len(basis), A=A, basis=basis)
-
-
-def _on_grid(gate, omega):
-    from .pulse_sequence import _same_grid
-    return gate.is_cached('control_matrix') and _same_grid(gate.omega, omega)
 
 
 def pass_bytes(max_length, d, A, W, n_out):
@@ -95,21 +36,9 @@ def table_bytes(n_gates, d, A, W):
 def _run_pass(gates, indices, plan, omega, S, idx, want_U, want_F):
     """One pass over the sequences *indices* (int32 arrays into *gates*): (infidelities or None, total propagators or
     None, filter functions or None)."""
-    d, N, A = plan['d'], plan['N'], plan['A']
+    d, A = plan['d'], plan['A']
     W, P = len(omega), len(indices)
-    used = np.unique(np.concatenate(indices))
-    slot_of = np.full(len(gates), -1, dtype=np.int32)
-    slot_of[used] = np.arange(len(used), dtype=np.int32)
-    table_gates = [gates[k] for k in used]
-    sources = [resident_source(g, d, W, N, A) for g in table_gates]
-    host = [g for g, src in zip(table_gates, sources) if src is None]
-    table = as_c128(np.array([g.get_control_matrix(omega) for g in host])) if host else None
-    handles = (ctypes.c_void_p*len(table_gates))(*[None if src is None else src[0].value for src in sources])
-    slots = np.array([-1 if src is None else src[1] for src in sources], dtype=np.int32)
-    U = as_c128(np.array([g.total_propagator for g in table_gates]))
-    tau = np.array([g.tau for g in table_gates], dtype=np.float64)
-    offsets, index, _ = pack_sequences([slot_of[i] for i in indices])
-    basis = as_c128(np.asarray(plan['basis']))
+    table = PassTable(gates, indices, plan, omega)
     infid = total = F = None
     args = [None, 0, 0, None, 0]
     if S is not None:
@@ -121,10 +50,8 @@ def _run_pass(gates, indices, plan, omega, S, idx, want_U, want_F):
     if want_F:
         F = np.empty((P, A, A, W), dtype=np.complex128)
     check(_lib.load().ffk_sequence_infidelities(
-        handles, slots.ctypes.data, None if table is None else table.ctypes.data, U.ctypes.data, tau.ctypes.data,
-        len(table_gates), offsets.ctypes.data, index.ctypes.data, P, omega.ctypes.data, W, basis.ctypes.data, 1, d, A,
-        N, *args, d, None if infid is None else infid.ctypes.data, None if total is None else total.ctypes.data,
-        None if F is None else F.ctypes.data))
+        *table.c_arguments(), *args, d, None if infid is None else infid.ctypes.data,
+        None if total is None else total.ctypes.data, None if F is None else F.ctypes.data))
     return infid, total, F
 
 
@@ -176,27 +103,13 @@ def sequence_infidelities(gates, sequences, spectrum, omega, n_oper_identifiers=
 
     Every other gate set evaluates the loop's expression for every sequence inside this call.
     """
-    from .pulse_sequence import PulseSequence
-    gates = list(gates)
-    for gate in gates:
-        if not isinstance(gate, PulseSequence):
-            raise TypeError('Can only concatenate PulseSequences!')
-    indices = index_arrays(sequences, len(gates))
-    if not indices:
-        raise ValueError('Need at least one sequence.')
+    gates, indices = validated(gates, sequences)
     want_U, want_F = bool(return_propagators), bool(return_filter_functions)
 
     def answer(infid, total, F):
         extras = ([total] if want_U else []) + ([F] if want_F else [])
         return (infid, *extras) if extras else infid
-    plan = eligibility(gates)
-    if plan is not None:
-        missing = [g for g in gates if not _on_grid(g, omega)]
-        if missing:
-            from .batch import get_filter_functions
-            get_filter_functions(missing, omega)
-        if not all('total_propagator' in g._data for g in gates):
-            plan = None
+    plan = batched_plan(gates, omega)
     if plan is None:
         return answer(*_loop(gates, indices, spectrum, omega, n_oper_identifiers, want_U, want_F))
     omega = as_f64(omega)

@@ -10,16 +10,14 @@ sequences' control matrices are never written to memory: the decay amplitudes ar
 concatenation-rule kernel at the end of each sequence, for every spectrum of the call (``stacked=True``) in one walk of
 the sequences.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib, util
+from ._gate_table import PassTable, batched_plan, validated
 from ._lib import as_c128, as_f64, check
 from .batch import MAX_PULSES, PASS_BYTES, split_passes
 from .processes import _single
-from .sequence_infidelities import _on_grid, eligibility, index_arrays
-from .sequences import pack_sequences, resident_source
+from .sequence_infidelities import eligibility, index_arrays  # noqa: F401
 
 __all__ = ['sequence_decay_amplitudes', 'sequence_cumulant_functions', 'sequence_error_transfer_matrices']
 
@@ -92,21 +90,9 @@ def _real_weights(parsed):
 def _run_pass(gates, indices, plan, omega, S, idx, stage, want_U):
     """One call of ``ffk_sequence_processes`` over the sequences *indices* (int32 arrays into *gates*) and the spectra
     S (K, W) or (K, n_idx, W): (values (K, P, ...), not finite (K, P), total propagators (P, d, d) or None)."""
-    d, N, A = plan['d'], plan['N'], plan['A']
-    W, P, K = len(omega), len(indices), len(S)
-    used = np.unique(np.concatenate(indices))
-    slot_of = np.full(len(gates), -1, dtype=np.int32)
-    slot_of[used] = np.arange(len(used), dtype=np.int32)
-    table_gates = [gates[k] for k in used]
-    sources = [resident_source(g, d, W, N, A) for g in table_gates]
-    host = [g for g, src in zip(table_gates, sources) if src is None]
-    table = as_c128(np.array([g.get_control_matrix(omega) for g in host])) if host else None
-    handles = (ctypes.c_void_p*len(table_gates))(*[None if src is None else src[0].value for src in sources])
-    slots = np.array([-1 if src is None else src[1] for src in sources], dtype=np.int32)
-    U = as_c128(np.array([g.total_propagator for g in table_gates]))
-    tau = np.array([g.tau for g in table_gates], dtype=np.float64)
-    offsets, index, _ = pack_sequences([slot_of[i] for i in indices])
-    basis = as_c128(np.asarray(plan['basis']))
+    d, N = plan['d'], plan['N']
+    P, K = len(indices), len(S)
+    table = PassTable(gates, indices, plan, omega)
     single_qubit = int(d == 2 and getattr(plan['basis'], 'btype', None) in ('Pauli', 'GGM'))
     idx = np.ascontiguousarray(idx, dtype=np.int32)
     n_idx = len(idx)
@@ -115,10 +101,8 @@ def _run_pass(gates, indices, plan, omega, S, idx, stage, want_U):
     flags = np.zeros((K, P), dtype=np.int32)
     total = np.empty((P, d, d), dtype=np.complex128) if want_U else None
     check(_lib.load().ffk_sequence_processes(
-        handles, slots.ctypes.data, None if table is None else table.ctypes.data, U.ctypes.data, tau.ctypes.data,
-        len(table_gates), offsets.ctypes.data, index.ctypes.data, P, omega.ctypes.data, W, basis.ctypes.data, 1, d, A,
-        N, single_qubit, S.ctypes.data, S.ndim - 1, K, idx.ctypes.data, n_idx, _STAGES[stage], out.ctypes.data,
-        flags.ctypes.data, None if total is None else total.ctypes.data))
+        *table.c_arguments(), single_qubit, S.ctypes.data, S.ndim - 1, K, idx.ctypes.data, n_idx, _STAGES[stage],
+        out.ctypes.data, flags.ctypes.data, None if total is None else total.ctypes.data))
     if stage == 'error_transfer_matrix':
         bad = flags != 0
     else:
@@ -143,14 +127,7 @@ def _loop(stage, gates, indices, spectra, omega, n_oper_identifiers, want_U):
 
 
 def _results(stage, gates, sequences, spectrum, omega, n_oper_identifiers, stacked, return_propagators):
-    from .pulse_sequence import PulseSequence
-    gates = list(gates)
-    for gate in gates:
-        if not isinstance(gate, PulseSequence):
-            raise TypeError('Can only concatenate PulseSequences!')
-    indices = index_arrays(sequences, len(gates))
-    if not indices:
-        raise ValueError('Need at least one sequence.')
+    gates, indices = validated(gates, sequences)
     spectra = stacked_spectra(spectrum, stacked)
     want_U = bool(return_propagators)
 
@@ -158,14 +135,7 @@ def _results(stage, gates, sequences, spectrum, omega, n_oper_identifiers, stack
         values = values if stacked else values[0]
         return (values, total) if want_U else values
     # routing, once per call: the gate set, then the spectra
-    plan = eligibility(gates) if all(S.ndim in (1, 2) for S in spectra) and len(omega) >= 2 else None
-    if plan is not None:
-        missing = [g for g in gates if not _on_grid(g, omega)]
-        if missing:
-            from .batch import get_filter_functions
-            get_filter_functions(missing, omega)
-        if not all('total_propagator' in g._data for g in gates):
-            plan = None
+    plan = batched_plan(gates, omega) if all(S.ndim in (1, 2) for S in spectra) and len(omega) >= 2 else None
     S = None
     if plan is not None:
         omega = as_f64(omega)

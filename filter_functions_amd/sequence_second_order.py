@@ -10,16 +10,14 @@ nothing of size W N^2 exists: the gates' own frequency shifts come from one ``ff
 and one walk of each sequence adds their rotations and the Gram matrices of the first-order rule's summands with their
 running sum, for every spectrum of the call (``stacked=True``).
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib, util
-from ._lib import as_c128, as_f64, check
+from ._gate_table import PassTable, batched_plan, validated
+from ._lib import as_f64, check
 from .batch import MAX_PULSES, PASS_BYTES, split_passes
-from .sequence_infidelities import _on_grid, eligibility, index_arrays
+from .sequence_infidelities import eligibility, index_arrays  # noqa: F401
 from .sequence_processes import _real_weights, stacked_spectra
-from .sequences import pack_sequences, resident_source
 
 __all__ = ['sequence_frequency_shifts']
 
@@ -58,32 +56,18 @@ def _run_pass(gates, indices, plan, omega, S, idx, shifts, want_U):
     """One call of ``ffk_sequence_frequency_shifts`` over the sequences *indices* (int32 arrays into *gates*), the
     spectra S (K, W) or (K, n_idx, W) and the gates' own frequency shifts (K, T, n_idx, N, N): (values (K, P, n_idx,
     N, N), not finite (K, P), total propagators (P, d, d) or None)."""
-    d, N, A = plan['d'], plan['N'], plan['A']
-    W, P, K = len(omega), len(indices), len(S)
-    used = np.unique(np.concatenate(indices))
-    slot_of = np.full(len(gates), -1, dtype=np.int32)
-    slot_of[used] = np.arange(len(used), dtype=np.int32)
-    table_gates = [gates[k] for k in used]
-    sources = [resident_source(g, d, W, N, A) for g in table_gates]
-    host = [g for g, src in zip(table_gates, sources) if src is None]
-    table = as_c128(np.array([g.get_control_matrix(omega) for g in host])) if host else None
-    handles = (ctypes.c_void_p*len(table_gates))(*[None if src is None else src[0].value for src in sources])
-    slots = np.array([-1 if src is None else src[1] for src in sources], dtype=np.int32)
-    U = as_c128(np.array([g.total_propagator for g in table_gates]))
-    tau = np.array([g.tau for g in table_gates], dtype=np.float64)
-    offsets, index, _ = pack_sequences([slot_of[i] for i in indices])
-    basis = as_c128(np.asarray(plan['basis']))
+    d, N = plan['d'], plan['N']
+    P, K = len(indices), len(S)
+    table = PassTable(gates, indices, plan, omega)
     idx = np.ascontiguousarray(idx, dtype=np.int32)
     n_idx = len(idx)
-    own = as_f64(np.ascontiguousarray(np.asarray(shifts)[:, used]))
+    own = as_f64(np.ascontiguousarray(np.asarray(shifts)[:, table.used]))
     out = np.empty((K, P, n_idx, N, N), dtype=np.float64)
     flags = np.zeros((K, P), dtype=np.int32)
     total = np.empty((P, d, d), dtype=np.complex128) if want_U else None
     check(_lib.load().ffk_sequence_frequency_shifts(
-        handles, slots.ctypes.data, None if table is None else table.ctypes.data, U.ctypes.data, tau.ctypes.data,
-        len(table_gates), offsets.ctypes.data, index.ctypes.data, P, omega.ctypes.data, W, basis.ctypes.data, 1, d, A,
-        N, S.ctypes.data, S.ndim - 1, K, idx.ctypes.data, n_idx, own.ctypes.data, out.ctypes.data, flags.ctypes.data,
-        None if total is None else total.ctypes.data))
+        *table.c_arguments(), S.ctypes.data, S.ndim - 1, K, idx.ctypes.data, n_idx, own.ctypes.data, out.ctypes.data,
+        flags.ctypes.data, None if total is None else total.ctypes.data))
     return out, flags != 0, total
 
 
@@ -145,14 +129,7 @@ def sequence_frequency_shifts(gates, sequences, spectrum, omega, n_oper_identifi
     and a sequence of one gate returns that gate's frequency shifts.  Everything else -- cross-spectra, other
     dimensions, ineligible gate sets -- and every (spectrum, sequence) whose result is not finite evaluates the loop's
     expression inside the call.  Pulse correlations are not offered."""
-    from .pulse_sequence import PulseSequence
-    gates = list(gates)
-    for gate in gates:
-        if not isinstance(gate, PulseSequence):
-            raise TypeError('Can only concatenate PulseSequences!')
-    indices = index_arrays(sequences, len(gates))
-    if not indices:
-        raise ValueError('Need at least one sequence.')
+    gates, indices = validated(gates, sequences)
     spectra = stacked_spectra(spectrum, stacked)
     want_U = bool(return_propagators)
 
@@ -160,14 +137,7 @@ def sequence_frequency_shifts(gates, sequences, spectrum, omega, n_oper_identifi
         values = values if stacked else values[0]
         return (values, total) if want_U else values
     # routing, once per call: the gate set, then the spectra
-    plan = eligibility(gates) if all(S.ndim in (1, 2) for S in spectra) and len(omega) >= 2 else None
-    if plan is not None:
-        missing = [g for g in gates if not _on_grid(g, omega)]
-        if missing:
-            from .batch import get_filter_functions
-            get_filter_functions(missing, omega)
-        if not all('total_propagator' in g._data for g in gates):
-            plan = None
+    plan = batched_plan(gates, omega) if all(S.ndim in (1, 2) for S in spectra) and len(omega) >= 2 else None
     S = None
     if plan is not None:
         omega = as_f64(omega)

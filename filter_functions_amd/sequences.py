@@ -204,13 +204,8 @@ def _run_pass(plans, members):
             if id(gate) not in slot_of:
                 slot_of[id(gate)] = len(gates)
                 gates.append(gate)
-    sources = [_gate_source(g, W, A) for g in gates]
-    host = [g for g, src in zip(gates, sources) if src is None]
-    gate_table = np.array([g.get_control_matrix(omega) for g in host]) if host else None
-    handles = [None if src is None else src[0].value for src in sources]
-    slots = [-1 if src is None else src[1] for src in sources]
-    propagators = np.array([g.total_propagator for g in gates])
-    tau = np.array([g.tau for g in gates], dtype=float)
+    from ._gate_table import staged_gates            # (which imports this module)
+    handles, slots, gate_table, propagators, tau = staged_gates(gates, omega, 2, 4, A)
     indices = [np.array([slot_of[id(g)] for g in plan['distinct']], dtype=np.int32)[plan['index']] for plan in group]
     offsets, index, _ = pack_sequences(indices)
     batch = SequencePass()

@@ -117,16 +117,20 @@ def staged_gates(table_gates, omega, d, N, A):
 class PassTable:
     """The table of one pass over the sequences *indices* (int32 arrays into *gates*) of a gate set routed by *plan*:
     only the gates the pass uses are in it, and the sequences are renumbered to index it (CSR ``offsets``, ``index``).
-    ``used`` are the positions in *gates* of the table's ``gates``."""
+    ``used`` are the positions in *gates* of the table's ``gates``.  *extra* (optional): further int32 arrays into
+    *gates*, one per sequence, whose gates the table holds as well; ``extra`` is then their concatenation, renumbered
+    like ``index`` (else None)."""
 
-    def __init__(self, gates, indices, plan, omega):
+    def __init__(self, gates, indices, plan, omega, extra=None):
         self.d, self.N, self.A = plan['d'], plan['N'], plan['A']
-        self.used = np.unique(np.concatenate(indices))
+        self.used = np.unique(np.concatenate(list(indices) + list(extra or [])))
         slot_of = np.full(len(gates), -1, dtype=np.int32)
         slot_of[self.used] = np.arange(len(self.used), dtype=np.int32)
         self.gates = [gates[k] for k in self.used]
         self.handles, self.slots, self.table, self.U, self.tau = staged_gates(self.gates, omega, self.d, self.N, self.A)
         self.offsets, self.index, _ = pack_sequences([slot_of[i] for i in indices])
+        self.extra = None if extra is None else np.ascontiguousarray(np.concatenate([slot_of[e] for e in extra]),
+                                                                     dtype=np.int32)
         self.omega = omega
         self.basis = as_c128(np.asarray(plan['basis']))
 

@@ -1750,6 +1750,133 @@ int ffk_sequence_frequency_shifts(ffk_resident* const* gates, const int32_t* slo
     return FFK_OK;
 }
 
+// ---- infidelities or decay amplitudes of every prefix of many sequences from one gate table in ONE pass, under any
+//      number of spectra (ff.sequence_prefix_infidelities, ff.sequence_prefix_decay_amplitudes; sequence_prefix.hip) --
+namespace {
+
+struct SeqPrefixLayout {
+    GateTableLayout table;
+    size_t S, idx, closing, inputs_end;                                                           // one H2D
+    size_t out, outputs_end;                                                                      // one D2H
+    size_t phases, L, Q, scale, partial, end;                                                     // device only
+};
+
+// doubles of one (position, spectrum, operator) in `out` and in the frequency blocks' partial sums
+size_t seq_prefix_out_tile(int N, int mode) { return mode == 2 ? size_t(N)*N : mode == 1 ? size_t(N) : 1; }
+size_t seq_prefix_partial_tile(int N, int mode) { return mode == 2 ? size_t(N)*N : size_t(N); }
+
+SeqPrefixLayout seq_prefix_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W, int n_idx,
+                                  int s_ndim, int n_spectra, int mode, bool has_closing) {
+    SeqPrefixLayout L;
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N;
+    const size_t rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
+    const size_t members = size_t(n_spectra)*n_index*n_idx;
+    const int width = ffk::sequence_prefix_block_width(d, A);
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.table = gate_table_layout(put, T, P, n_index, n_host, d, A, N, W);
+    L.S = put(16*rows*W);
+    L.idx = put(4*size_t(n_idx));
+    L.closing = put(has_closing ? 4*n_index : 0);
+    L.inputs_end = o;
+    L.out = put(8*members*seq_prefix_out_tile(N, mode));
+    L.outputs_end = o;
+    L.phases = put(16*size_t(T)*W);
+    L.L = put(8*size_t(T)*nn);
+    L.Q = put(16*size_t(P)*dd);
+    L.scale = put(16*rows*W);
+    L.partial = put(8*size_t((W + width - 1)/width)*members*seq_prefix_partial_tile(N, mode));
+    L.end = o;
+    return L;
+}
+
+bool seq_prefix_shape_ok(int T, int P, int d, int A, int N, int W, int n_idx, int s_ndim, int n_spectra, int mode) {
+    return seq_infid_shape_ok(T, P, d, A, N, W) && W >= 2 && (s_ndim == 1 || s_ndim == 2) && n_idx >= 1 &&
+           n_idx <= A && n_spectra >= 1 && n_spectra <= 65535 && mode >= 0 && mode <= 2;
+}
+
+}  // namespace
+
+size_t ffk_sequence_prefix_processes_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                                     int n_idx, int s_ndim, int n_spectra, int mode, int has_closing) {
+    if (!seq_prefix_shape_ok(T, P, d, A, N, W, n_idx, s_ndim, n_spectra, mode) || n_index < P || n_host < 0 ||
+        n_host > T)
+        return 0;
+    return seq_prefix_layout(T, P, size_t(n_index), n_host, d, A, N, W, n_idx, s_ndim, n_spectra, mode,
+                             has_closing != 0).end;
+}
+
+int ffk_sequence_prefix_processes(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                  const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                                  const int32_t* index, int P, const double* omega, int W, const double* basis,
+                                  int hermitian_basis, int d, int A, int N, const int32_t* closing,
+                                  const double* spectrum, int s_ndim, int n_spectra, const int32_t* idx, int n_idx,
+                                  int mode, double* out) {
+    const GateTable g{gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                      hermitian_basis, d, A, N};
+    FFK_REQUIRE(spectrum && idx && out, "NULL argument");
+    FFK_REQUIRE(ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A),
+                "unsupported shape d=%d N=%d A=%d (need (d, N) = (2, 4) or (4, 16), 1 <= A <= 4)", d, N, A);
+    size_t n_index = 0;
+    if (int rc = check_gate_table(g, 2, &n_index)) return rc;
+    FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
+    FFK_REQUIRE(n_spectra >= 1 && n_spectra <= 65535, "n_spectra = %d, need 1 ... 65535", n_spectra);
+    FFK_REQUIRE(mode >= 0 && mode <= 2, "mode = %d, need 0 (infidelities), 1 (diagonal of the decay amplitudes) or 2 "
+                "(decay amplitudes)", mode);
+    if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d, true)) return rc;
+    for (int i = 0; i < n_idx; ++i)
+        for (int m = 0; m < i; ++m)
+            FFK_REQUIRE(idx[i] != idx[m], "idx[%d] = idx[%d] = %d: the selected operators must be distinct", m, i,
+                        idx[i]);
+    if (closing)
+        for (size_t k = 0; k < n_index; ++k)
+            FFK_REQUIRE(closing[k] >= 0 && closing[k] < T, "closing[%zu] = %d outside [0, %d)", k, closing[k], T);
+    const size_t members = size_t(n_spectra)*n_index*n_idx;
+    FFK_REQUIRE(members*seq_prefix_partial_tile(N, mode) <= (size_t(1) << 32),
+                "%zu prefix results exceed one pass", members);
+    const size_t s_rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    std::vector<const unsigned char*> tab;
+    int n_host = 0;
+    if (int rc = locate_gates(g, dev, &tab, &n_host)) return rc;
+    const SeqPrefixLayout L = seq_prefix_layout(T, P, n_index, n_host, d, A, N, W, n_idx, s_ndim, n_spectra, mode,
+                                                closing != nullptr);
+    PinLease pin;
+    if (int rc = pin.take(L.outputs_end, dev)) return rc;
+    unsigned char* hp = pin.ptr();
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    void* base = nullptr;
+    if (int rc = arena_reserve(L.end, &base)) return rc;
+    unsigned char* dp = static_cast<unsigned char*>(base);
+    stage_gate_table(g, L.table, n_index, longest_first(offsets, P).data(), &tab, hp, dp);
+    stage_spectrum(spectrum, true, s_rows*W, idx, n_idx, hp + L.S, hp + L.idx);
+    if (closing) std::memcpy(hp + L.closing, closing, 4*n_index);
+    StreamDrain drain{s};
+    auto at = [dp](size_t off) { return dp + off; };
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    const GateTableDevice D(dp, L.table);
+    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.idx));
+    cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
+    double* dL = reinterpret_cast<double*>(at(L.L));
+    cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
+    FFK_HIP(launch_gate_table_front(g, D, dPh, dL, reinterpret_cast<cplx*>(at(L.Q)), s));
+    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(s_rows), W, D.omega, W, 0, dScale,
+                                         s));
+    FFK_HIP(ffk::launch_sequence_prefix(d, dPh, D.tab, dL, D.offsets, D.index,
+                                        closing ? reinterpret_cast<const int32_t*>(at(L.closing)) : nullptr, D.order, P,
+                                        n_index, T, A, W, dScale, s_ndim, n_spectra, dIdx, n_idx, mode,
+                                        reinterpret_cast<double*>(at(L.partial)),
+                                        reinterpret_cast<double*>(at(L.out)), s));
+    FFK_HIP(hipMemcpyAsync(hp + L.out, dp + L.out, L.outputs_end - L.out, hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    if (int rc = kernel_fault_status()) return rc;
+    std::memcpy(out, hp + L.out, 8*members*seq_prefix_out_tile(N, mode));
+    return FFK_OK;
+}
+
 }  // extern "C"
 
 #if defined(FFK_HOST_SANITIZE)
@@ -1946,6 +2073,15 @@ extern "C" int ffk_selftest_host(int rounds, unsigned seed, char* report, int re
                 if (!ascending(HL) || HL.partial + 8*size_t((W + 63)/64)*ks*P*si*16 > HL.end ||
                     HL.end != ffk_sequence_frequency_shifts_workspace_bytes(T, P, n_index, n_host, 2, As, 4, W, si, sn, ks))
                     return -17;
+                // the prefix pass: what the query reports, the partial sums of every position inside it
+                const int pm = pick(0, 2), pc = pick(0, 1);
+                const SeqPrefixLayout XL = seq_prefix_layout(T, P, size_t(n_index), n_host, 2, As, 4, W, si, sn, ks, pm,
+                                                             pc != 0);
+                if (!ascending(XL) ||
+                    XL.partial + 8*size_t((W + 63)/64)*ks*n_index*si*seq_prefix_partial_tile(4, pm) > XL.end ||
+                    XL.end != ffk_sequence_prefix_processes_workspace_bytes(T, P, n_index, n_host, 2, As, 4, W, si, sn,
+                                                                            ks, pm, pc))
+                    return -27;
                 // the process pass of the sequences, two-qubit gates: any stage, the cumulant workspace last (below stage
                 // 3 the requested array IS `out`, so gamma or K names an earlier offset a second time)
                 const int stage = pick(1, 3);

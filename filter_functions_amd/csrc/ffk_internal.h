@@ -422,6 +422,24 @@ hipError_t launch_sequence_second_order(int d, const cplx* phases, const cplx* c
                                         const int32_t* idx, int n_idx, const double* gate_shifts, double* partial,
                                         double* out, hipStream_t stream);
 
+// ---- sequence_prefix.hip ----------------------------------------------------------------------
+// Infidelities (mode 0), diagonals of the decay amplitudes (mode 1) or decay amplitudes (mode 2) of every prefix of
+// the sequences of such a pass (d = 2 or 4), after the front launch of its dimension: one forward walk of each
+// sequence with an epilogue per position, then the sum of the frequency blocks' partial tiles in index order (two
+// launches whatever P, n_index and n_spectra; grid z carries the spectra beyond sequence_prefix_spectra_per_walk()).
+// closing (n_index) or NULL: the table row of the gate appended behind the prefix that ends at each position.  scale
+// as for launch_sequences_gamma; idx holds distinct operators.  partial (ceil(W / block width), n_index, n_spectra,
+// n_idx, N[, N]) f64 scratch ([N][N] at mode 2); out (n_spectra, n_index, n_idx[, N[, N]]) f64.  The block width depends
+// on d and A alone.
+int sequence_prefix_block_width(int d, int A);
+int sequence_prefix_spectra_per_walk();
+bool sequence_prefix_staged(int d, int T, int A);
+hipError_t launch_sequence_prefix(int d, const cplx* phases, const cplx* const* Rtab, const double* Lpulse,
+                                  const int32_t* offsets, const int32_t* index, const int32_t* closing,
+                                  const int32_t* order, int P, size_t n_index, int T, int A, int W, const cplx* scale,
+                                  int s_ndim, int n_spectra, const int32_t* idx, int n_idx, int mode, double* partial,
+                                  double* out, hipStream_t stream);
+
 // ---- correlations.hip -------------------------------------------------------------------------
 // Pulse-correlation infidelities of many sequences from one gate table (d = 2, N = 4, A <= 4, at most
 // correlation_max_length() positions each), after launch_sequences_front.  Prefix: Qc (n_index, N, N) f64, the

@@ -829,6 +829,33 @@ int ffk_sequence_frequency_shifts(ffk_resident* const* gates, const int32_t* slo
                                   int n_spectra, const int32_t* idx, int n_idx, const double* gate_shifts, double* out,
                                   int32_t* not_finite, double* total_propagators);
 
+/* ---- infidelities or decay amplitudes of every PREFIX of many gate sequences from one gate set in ONE pass, under
+ *      any number of spectra (ff.sequence_prefix_infidelities, ff.sequence_prefix_decay_amplitudes) ----
+ * Sequences, gates, slots, gate_table, gate_propagators, tau, omega, basis, spectrum, s_ndim, n_spectra and idx as for
+ * ffk_sequence_frequency_shifts (Hermitian basis; (d, N) = (2, 4) or (4, 16), 1 <= A <= 4; W >= 2; real weights of
+ * one or two dimensions; distinct operators in idx).  closing (n_index,) int32 host or NULL: closing[offsets[p] + g]
+ * is the table row, in [0, T), of the gate appended behind the first g + 1 gates of sequence p.  The result of global
+ * position offsets[p] + g is that of the sequence index[offsets[p] : offsets[p] + g + 1] (with its closing gate):
+ * mode 0 the infidelities, out (n_spectra, n_index, n_idx) f64 host, the trace of the decay amplitudes over d; mode 1
+ * the diagonal of the decay amplitudes, out (n_spectra, n_index, n_idx, N); mode 2 the decay amplitudes, out
+ * (n_spectra, n_index, n_idx, N, N).  The control matrix of a prefix is the partial sum of the concatenation rule,
+ * which a forward walk holds in registers at every position: each sequence is walked once, G positions instead of
+ * the G (G + 1) / 2 of its prefixes taken as sequences, with one epilogue per position.  One H2D copy, four launches
+ * whatever P, n_index and n_spectra -- the front, the weights, the walk (two spectra share a walk, grid z carries the
+ * further pairs), the sum of the frequency blocks' partial results in block order --, one D2H copy.  Arena workspace,
+ * no result handle.  A position's result is the same bits whatever else is in the pass, whatever lies behind it in
+ * its sequence and however many spectra the call carries; decay amplitudes are symmetric bit for bit.  Bad arguments
+ * (a closing entry outside [0, T) among them): FFK_EINVAL before anything touches the device.  The workspace query
+ * needs no GPU (0: unsupported shape). */
+size_t ffk_sequence_prefix_processes_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N, int W,
+                                                     int n_idx, int s_ndim, int n_spectra, int mode, int has_closing);
+int ffk_sequence_prefix_processes(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                  const double* gate_propagators, const double* tau, int T, const int32_t* offsets,
+                                  const int32_t* index, int P, const double* omega, int W, const double* basis,
+                                  int hermitian_basis, int d, int A, int N, const int32_t* closing,
+                                  const double* spectrum, int s_ndim, int n_spectra, const int32_t* idx, int n_idx,
+                                  int mode, double* out);
+
 /* ---- one-sided all-gather of the F blocks over xGMI (frequency-sharded step; the
  *      reference has no multi-device path: numeric.py:846-869 is embarrassingly parallel in omega
  *      and this is the exchange that reassembles F(omega) for util.integrate, util.py:880-906) ----

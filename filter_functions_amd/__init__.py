@@ -14,7 +14,8 @@ side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
 from . import (analytic, basis, batch, batch_gradient, batch_second_order, correlations, gradient, numeric, processes, pulse_sequence, sequences,
-               sequence_prefixes, sequence_processes, sequence_second_order, superoperator, util)
+               sequence_prefix_second_order, sequence_prefixes, sequence_processes, sequence_second_order, superoperator,
+               util)
 from .basis import Basis
 from .batch import get_filter_functions, infidelities
 from .batch_gradient import filter_function_derivatives, infidelity_derivatives
@@ -28,6 +29,7 @@ from .sequence_correlations import sequence_correlation_infidelities
 from .sequence_infidelities import sequence_infidelities
 from .sequence_prefixes import (sequence_prefix_decay_amplitudes, sequence_prefix_infidelities,
                                 sequence_prefix_propagators)
+from .sequence_prefix_second_order import sequence_prefix_cumulant_functions, sequence_prefix_frequency_shifts
 from .sequence_processes import (sequence_cumulant_functions, sequence_decay_amplitudes,
                                  sequence_error_transfer_matrices)
 from .sequence_second_order import sequence_frequency_shifts
@@ -47,7 +49,8 @@ __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradie
            'pulse_sequence', 'remap', 'sequence_correlation_infidelities', 'sequence_correlations',
            'sequence_cumulant_functions', 'sequence_decay_amplitudes',
            'sequence_error_transfer_matrices', 'sequence_frequency_shifts', 'sequence_infidelities',
-           'sequence_prefix_decay_amplitudes', 'sequence_prefix_infidelities', 'sequence_prefix_propagators',
+           'sequence_prefix_cumulant_functions', 'sequence_prefix_decay_amplitudes', 'sequence_prefix_frequency_shifts',
+           'sequence_prefix_infidelities', 'sequence_prefix_propagators', 'sequence_prefix_second_order',
            'sequence_prefixes', 'sequence_processes',
            'sequence_second_order', 'sequences',
            'superoperator', 'util']

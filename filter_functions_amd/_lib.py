@@ -296,6 +296,12 @@ SIGNATURES = {
     'ffk_sequence_prefix_processes': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                               c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                               c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'ffk_sequence_prefix_frequency_shifts_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int,
+                                                                        c_int, c_int, c_int, c_int, c_int, c_int]),
+    'ffk_sequence_prefix_frequency_shifts': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                     c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                                     c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                                     c_int, c_void_p, c_void_p]),
     'ffk_ipc_get_handle': (c_int, [c_void_p, c_void_p]),
     'ffk_ipc_open_handle': (c_int, [c_void_p, POINTER(c_void_p)]),
     'ffk_ipc_close_handle': (c_int, [c_void_p]),

@@ -1877,6 +1877,124 @@ int ffk_sequence_prefix_processes(ffk_resident* const* gates, const int32_t* slo
     return FFK_OK;
 }
 
+// ---- frequency shifts (second order) of every prefix of many sequences from one gate table in ONE pass, under any
+//      number of spectra (ff.sequence_prefix_frequency_shifts; sequence_prefix_second_order.hip) ----------------------
+namespace {
+
+struct SeqPrefixShiftLayout {
+    GateTableLayout table;
+    size_t S, idx, closing, shifts, inputs_end;                                                   // one H2D
+    size_t out, outputs_end;                                                                      // one D2H
+    size_t phases, L, Q, scale, partial, end;                                                     // device only
+};
+
+SeqPrefixShiftLayout seq_prefix_shift_layout(int T, int P, size_t n_index, int n_host, int d, int A, int N, int W,
+                                             int n_idx, int s_ndim, int n_spectra, bool has_closing) {
+    SeqPrefixShiftLayout L;
+    const size_t dd = size_t(d)*d, nn = size_t(N)*N;
+    const size_t rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
+    const size_t tiles = size_t(n_spectra)*n_index*n_idx;
+    const int width = ffk::sequence_prefix_second_order_block_width(d, A);
+    size_t o = 0;
+    auto put = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
+    L.table = gate_table_layout(put, T, P, n_index, n_host, d, A, N, W);
+    L.S = put(16*rows*W);
+    L.idx = put(4*size_t(n_idx));
+    L.closing = put(has_closing ? 4*n_index : 0);
+    L.shifts = put(8*size_t(n_spectra)*T*n_idx*nn);
+    L.inputs_end = o;
+    L.out = put(8*tiles*nn);
+    L.outputs_end = o;
+    L.phases = put(16*size_t(T)*W);
+    L.L = put(8*size_t(T)*nn);
+    L.Q = put(16*size_t(P)*dd);
+    L.scale = put(16*rows*W);
+    L.partial = put(8*size_t((W + width - 1)/width)*tiles*nn);
+    L.end = o;
+    return L;
+}
+
+}  // namespace
+
+size_t ffk_sequence_prefix_frequency_shifts_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N,
+                                                            int W, int n_idx, int s_ndim, int n_spectra,
+                                                            int has_closing) {
+    if (!seq_shift_shape_ok(T, P, d, A, N, W, n_idx, s_ndim, n_spectra) || n_index < P || n_host < 0 || n_host > T)
+        return 0;
+    return seq_prefix_shift_layout(T, P, size_t(n_index), n_host, d, A, N, W, n_idx, s_ndim, n_spectra,
+                                   has_closing != 0).end;
+}
+
+int ffk_sequence_prefix_frequency_shifts(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                         const double* gate_propagators, const double* tau, int T,
+                                         const int32_t* offsets, const int32_t* index, int P, const double* omega,
+                                         int W, const double* basis, int hermitian_basis, int d, int A, int N,
+                                         const int32_t* closing, const double* spectrum, int s_ndim, int n_spectra,
+                                         const int32_t* idx, int n_idx, const double* gate_shifts, double* out) {
+    const GateTable g{gates, slots, gate_table, gate_propagators, tau, T, offsets, index, P, omega, W, basis,
+                      hermitian_basis, d, A, N};
+    FFK_REQUIRE(spectrum && idx && gate_shifts && out, "NULL argument");
+    FFK_REQUIRE(ffk::sequences_supported(d, N, A) || ffk::sequences4_supported(d, N, A),
+                "unsupported shape d=%d N=%d A=%d (need (d, N) = (2, 4) or (4, 16), 1 <= A <= 4)", d, N, A);
+    size_t n_index = 0;
+    if (int rc = check_gate_table(g, 2, &n_index)) return rc;
+    FFK_REQUIRE(s_ndim == 1 || s_ndim == 2, "spectrum of %d dimensions: cross-spectra are not integrated here", s_ndim);
+    FFK_REQUIRE(n_spectra >= 1 && n_spectra <= 65535, "n_spectra = %d, need 1 ... 65535", n_spectra);
+    if (int rc = check_spectrum_args(s_ndim, idx, n_idx, A, d, true)) return rc;
+    for (int i = 0; i < n_idx; ++i)
+        for (int m = 0; m < i; ++m)
+            FFK_REQUIRE(idx[i] != idx[m], "idx[%d] = idx[%d] = %d: the selected operators must be distinct", m, i,
+                        idx[i]);
+    if (closing)
+        for (size_t k = 0; k < n_index; ++k)
+            FFK_REQUIRE(closing[k] >= 0 && closing[k] < T, "closing[%zu] = %d outside [0, %d)", k, closing[k], T);
+    const size_t nn = size_t(N)*N;
+    const size_t tiles = size_t(n_spectra)*n_index*n_idx;
+    FFK_REQUIRE(tiles*nn <= (size_t(1) << 32), "%zu prefix tiles exceed one pass", tiles);
+    const size_t s_rows = size_t(n_spectra)*spectrum_shape(s_ndim, n_idx).rows;
+    int dev = 0;
+    FFK_HIP(hipGetDevice(&dev));
+    std::vector<const unsigned char*> tab;
+    int n_host = 0;
+    if (int rc = locate_gates(g, dev, &tab, &n_host)) return rc;
+    const SeqPrefixShiftLayout L = seq_prefix_shift_layout(T, P, n_index, n_host, d, A, N, W, n_idx, s_ndim, n_spectra,
+                                                           closing != nullptr);
+    PinLease pin;
+    if (int rc = pin.take(L.outputs_end, dev)) return rc;
+    unsigned char* hp = pin.ptr();
+    hipStream_t s;
+    if (int rc = resident_stream(&s)) return rc;
+    std::lock_guard<std::mutex> lock(g_arena.mu);
+    void* base = nullptr;
+    if (int rc = arena_reserve(L.end, &base)) return rc;
+    unsigned char* dp = static_cast<unsigned char*>(base);
+    stage_gate_table(g, L.table, n_index, longest_first(offsets, P).data(), &tab, hp, dp);
+    stage_spectrum(spectrum, true, s_rows*W, idx, n_idx, hp + L.S, hp + L.idx);
+    if (closing) std::memcpy(hp + L.closing, closing, 4*n_index);
+    std::memcpy(hp + L.shifts, gate_shifts, 8*size_t(n_spectra)*T*n_idx*nn);
+    StreamDrain drain{s};
+    auto at = [dp](size_t off) { return dp + off; };
+    FFK_HIP(hipMemcpyAsync(dp, hp, L.inputs_end, hipMemcpyHostToDevice, s));
+    const GateTableDevice D(dp, L.table);
+    const int32_t* dIdx = reinterpret_cast<const int32_t*>(at(L.idx));
+    cplx* dPh = reinterpret_cast<cplx*>(at(L.phases));
+    double* dL = reinterpret_cast<double*>(at(L.L));
+    cplx* dScale = reinterpret_cast<cplx*>(at(L.scale));
+    FFK_HIP(launch_gate_table_front(g, D, dPh, dL, reinterpret_cast<cplx*>(at(L.Q)), s));
+    FFK_HIP(ffk::launch_spectral_weights(reinterpret_cast<const cplx*>(at(L.S)), int(s_rows), W, D.omega, W, 0, dScale,
+                                         s));
+    FFK_HIP(ffk::launch_sequence_prefix_second_order(
+        d, dPh, D.tab, dL, D.offsets, D.index, closing ? reinterpret_cast<const int32_t*>(at(L.closing)) : nullptr,
+        D.order, P, n_index, T, A, W, dScale, s_ndim, n_spectra, dIdx, n_idx,
+        reinterpret_cast<const double*>(at(L.shifts)), reinterpret_cast<double*>(at(L.partial)),
+        reinterpret_cast<double*>(at(L.out)), s));
+    FFK_HIP(hipMemcpyAsync(hp + L.out, dp + L.out, L.outputs_end - L.out, hipMemcpyDeviceToHost, s));
+    FFK_HIP(hipStreamSynchronize(s));
+    if (int rc = kernel_fault_status()) return rc;
+    std::memcpy(out, hp + L.out, 8*tiles*nn);
+    return FFK_OK;
+}
+
 }  // extern "C"
 
 #if defined(FFK_HOST_SANITIZE)

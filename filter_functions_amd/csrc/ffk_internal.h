@@ -440,6 +440,24 @@ hipError_t launch_sequence_prefix(int d, const cplx* phases, const cplx* const* 
                                   int s_ndim, int n_spectra, const int32_t* idx, int n_idx, int mode, double* partial,
                                   double* out, hipStream_t stream);
 
+// ---- sequence_prefix_second_order.hip ---------------------------------------------------------
+// Frequency shifts of every prefix of the sequences of such a pass (d = 2 or 4), after the front launch of its
+// dimension: the forward walk of launch_sequence_second_order with an epilogue per position on copies of its
+// accumulators, then the sum of the frequency blocks' partial tiles in index order (two launches whatever P, n_index
+// and n_spectra; grid z carries the spectra beyond sequence_prefix_second_order_spectra_per_walk(), a function of d, A
+// and whether closing gates are given).  closing as for launch_sequence_prefix, gate_shifts (n_spectra, T, n_idx, N, N)
+// as for launch_sequence_second_order.  partial (ceil(W / block width), n_index, n_spectra, n_idx, N, N) f64 scratch;
+// out (n_spectra, n_index, n_idx, N, N) f64.  The block width depends on d and A alone.
+int sequence_prefix_second_order_block_width(int d, int A);
+int sequence_prefix_second_order_spectra_per_walk(int d, int A, bool closing);
+bool sequence_prefix_second_order_staged(int d, int T, int A, bool closing);
+hipError_t launch_sequence_prefix_second_order(int d, const cplx* phases, const cplx* const* Rtab, const double* Lpulse,
+                                               const int32_t* offsets, const int32_t* index, const int32_t* closing,
+                                               const int32_t* order, int P, size_t n_index, int T, int A, int W,
+                                               const cplx* scale, int s_ndim, int n_spectra, const int32_t* idx,
+                                               int n_idx, const double* gate_shifts, double* partial, double* out,
+                                               hipStream_t stream);
+
 // ---- correlations.hip -------------------------------------------------------------------------
 // Pulse-correlation infidelities of many sequences from one gate table (d = 2, N = 4, A <= 4, at most
 // correlation_max_length() positions each), after launch_sequences_front.  Prefix: Qc (n_index, N, N) f64, the

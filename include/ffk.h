@@ -856,6 +856,34 @@ int ffk_sequence_prefix_processes(ffk_resident* const* gates, const int32_t* slo
                                   const double* spectrum, int s_ndim, int n_spectra, const int32_t* idx, int n_idx,
                                   int mode, double* out);
 
+/* ---- frequency shifts (second order) of every PREFIX of many gate sequences from one gate set in ONE pass, under
+ *      any number of spectra (ff.sequence_prefix_frequency_shifts) ----
+ * The arguments of ffk_sequence_prefix_processes without mode (closing (n_index,) int32 host or NULL among them), and
+ * gate_shifts (n_spectra, T, n_idx, N, N) f64 host as for ffk_sequence_frequency_shifts: the gates' own frequency
+ * shifts under each spectrum.  out (n_spectra, n_index, n_idx, N, N) f64 host: the result of global position
+ * offsets[p] + g is the frequency shift of the sequence index[offsets[p] : offsets[p] + g + 1], with the gate
+ * closing[offsets[p] + g] appended if closing is given.  The forward walk of ffk_sequence_frequency_shifts holds the
+ * frequency shift of the first m gates in its accumulators after position m; a closing gate c adds one more summand
+ * of the same form from the state the walk holds,
+ *     Lam_{m+1}^T gate_shifts[c] Lam_{m+1} + sum_w c_w S(w) Re(conj((R_c Lam_{m+1})[k, w]) C_m[l, w]),
+ * so each sequence is walked once, G positions instead of the G (G + 1) / 2 of its prefixes taken as sequences, with
+ * one epilogue per position on copies of the accumulators.  One H2D copy, four launches whatever P, n_index and
+ * n_spectra -- the front, the weights, the walk (one or two spectra share a walk, a function of d, A and whether
+ * closing is given; grid z carries the further ones), the sum of the frequency blocks' partial tiles in block order
+ * --, one D2H copy.  Arena workspace, no result handle.  A position's result is the same bits whatever else is in the
+ * pass, whatever lies behind it in its sequence and however many spectra the call carries; without closing, position
+ * 0 of a sequence returns that gate's row of gate_shifts.  Bad arguments (a closing entry outside [0, T) among them):
+ * FFK_EINVAL before anything touches the device.  The workspace query needs no GPU (0: unsupported shape). */
+size_t ffk_sequence_prefix_frequency_shifts_workspace_bytes(int T, int P, int n_index, int n_host, int d, int A, int N,
+                                                            int W, int n_idx, int s_ndim, int n_spectra,
+                                                            int has_closing);
+int ffk_sequence_prefix_frequency_shifts(ffk_resident* const* gates, const int32_t* slots, const double* gate_table,
+                                         const double* gate_propagators, const double* tau, int T,
+                                         const int32_t* offsets, const int32_t* index, int P, const double* omega,
+                                         int W, const double* basis, int hermitian_basis, int d, int A, int N,
+                                         const int32_t* closing, const double* spectrum, int s_ndim, int n_spectra,
+                                         const int32_t* idx, int n_idx, const double* gate_shifts, double* out);
+
 /* ---- one-sided all-gather of the F blocks over xGMI (frequency-sharded step; the
  *      reference has no multi-device path: numeric.py:846-869 is embarrassingly parallel in omega
  *      and this is the exchange that reassembles F(omega) for util.integrate, util.py:880-906) ----

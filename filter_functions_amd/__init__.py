@@ -13,7 +13,7 @@ The arithmetic runs in hand-written HIP kernels for gfx950 behind a C ABI
 side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
-from . import (analytic, basis, batch, batch_gradient, batch_second_order, correlations, gradient, numeric, processes, pulse_sequence, sequences,
+from . import (analytic, basis, batch, batch_gradient, batch_second_order, correlations, expm_batch, gradient, numeric, processes, pulse_sequence, sequences,
                sequence_prefix_second_order, sequence_prefixes, sequence_processes, sequence_second_order, superoperator,
                util)
 from .basis import Basis
@@ -21,6 +21,7 @@ from .batch import get_filter_functions, infidelities
 from .batch_gradient import filter_function_derivatives, infidelity_derivatives
 from .batch_second_order import frequency_shifts
 from .correlations import correlation_infidelities
+from .expm_batch import exponentiate_cumulant_functions
 from .gradient import infidelity_derivative
 from .numeric import error_transfer_matrix, infidelity
 from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
@@ -29,7 +30,8 @@ from .sequence_correlations import sequence_correlation_infidelities
 from .sequence_infidelities import sequence_infidelities
 from .sequence_prefixes import (sequence_prefix_decay_amplitudes, sequence_prefix_infidelities,
                                 sequence_prefix_propagators)
-from .sequence_prefix_second_order import sequence_prefix_cumulant_functions, sequence_prefix_frequency_shifts
+from .sequence_prefix_second_order import (sequence_prefix_cumulant_functions, sequence_prefix_error_transfer_matrices,
+                                           sequence_prefix_frequency_shifts)
 from .sequence_processes import (sequence_cumulant_functions, sequence_decay_amplitudes,
                                  sequence_error_transfer_matrices)
 from .sequence_second_order import sequence_frequency_shifts
@@ -43,13 +45,14 @@ __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradie
            'concatenate_sequences',
            'correlation_infidelities', 'correlations',
            'concatenate_without_filter_function', 'cumulant_functions', 'decay_amplitudes',
-           'error_transfer_matrices', 'error_transfer_matrix', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
+           'error_transfer_matrices', 'error_transfer_matrix', 'expm_batch', 'exponentiate_cumulant_functions', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
            'filter_function_derivatives', 'frequency_shifts', 'infidelity_derivative', 'infidelity_derivatives',
            'liouville_representation', 'numeric', 'processes',
            'pulse_sequence', 'remap', 'sequence_correlation_infidelities', 'sequence_correlations',
            'sequence_cumulant_functions', 'sequence_decay_amplitudes',
            'sequence_error_transfer_matrices', 'sequence_frequency_shifts', 'sequence_infidelities',
-           'sequence_prefix_cumulant_functions', 'sequence_prefix_decay_amplitudes', 'sequence_prefix_frequency_shifts',
+           'sequence_prefix_cumulant_functions', 'sequence_prefix_decay_amplitudes',
+           'sequence_prefix_error_transfer_matrices', 'sequence_prefix_frequency_shifts',
            'sequence_prefix_infidelities', 'sequence_prefix_propagators', 'sequence_prefix_second_order',
            'sequence_prefixes', 'sequence_processes',
            'sequence_second_order', 'sequences',

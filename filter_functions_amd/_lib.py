@@ -8,7 +8,7 @@ a GPU.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_size_t, c_uint, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_long, c_size_t, c_uint, c_void_p
 
 import numpy as np
 
@@ -190,6 +190,9 @@ SIGNATURES = {
     'ffk_expm_real': (c_int, [c_void_p, c_int, c_void_p]),
     'ffk_error_transfer_matrix_workspace_bytes': (c_size_t, [c_int]),
     'ffk_error_transfer_matrix_dev': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'ffk_expm_real_batch_workspace_bytes': (c_size_t, [c_long, c_int, c_int]),
+    'ffk_expm_real_batch_dev': (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'ffk_expm_real_batch': (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
     'ffk_liouville': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     'ffk_liouville_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'ffk_liouville_dev': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,

@@ -490,5 +490,59 @@ int ffk_error_transfer_matrix_dev(const double* cumulant_function, int batch, in
     return FFK_OK;
 }
 
+// ---- exp of many small matrices at once (expm_batch.hip) ------------------------------------------
+namespace {
+// device bytes one chunk of the host-pointer call may hold in the arena
+constexpr size_t kExpmBatchArenaBytes = size_t(1) << 30;
+
+int expm_batch_check(const void* tiles, long count, int rows, int N, const void* result, const void* not_finite) {
+    FFK_REQUIRE(tiles && result && not_finite, "NULL argument");
+    FFK_REQUIRE(count >= 0, "count = %ld is negative", count);
+    FFK_REQUIRE(rows >= 1, "rows = %d: every matrix is the sum of at least one tile", rows);
+    FFK_REQUIRE(N >= 1 && N <= 16, "matrix dimension %d outside [1, 16]", N);
+    return FFK_OK;
+}
+// the three arrays of `count` matrices: tiles, result, flags
+size_t expm_batch_bytes(size_t count, int rows, int N) {
+    const size_t nn = size_t(N)*N;
+    return align_up(8*count*rows*nn) + align_up(8*count*nn) + align_up(4*count);
+}
+}  // namespace
+
+size_t ffk_expm_real_batch_workspace_bytes(long count, int rows, int N) {
+    if (count < 0 || rows < 1 || N < 1 || N > 16) return 0;
+    return expm_batch_bytes(size_t(count), rows, N);
+}
+
+int ffk_expm_real_batch_dev(const double* tiles, long count, int rows, int N, double* result, int32_t* not_finite,
+                            void* stream) {
+    if (int rc = expm_batch_check(tiles, count, rows, N, result, not_finite)) return rc;
+    if (count == 0) return FFK_OK;
+    // launches only: the squarings are chosen inside the kernel, nothing comes back to the host
+    FFK_HIP(ffk::launch_expm_batch(tiles, count, rows, N, result, not_finite, static_cast<hipStream_t>(stream)));
+    return FFK_OK;
+}
+
+int ffk_expm_real_batch(const double* tiles, long count, int rows, int N, double* result, int32_t* not_finite) {
+    if (int rc = expm_batch_check(tiles, count, rows, N, result, not_finite)) return rc;
+    const size_t nn = size_t(N)*N;
+    // chunks of what the arena budget takes (one matrix at least): a copy in, a launch, the results and flags out
+    const size_t one = 8*size_t(rows)*nn + 8*nn + 4;
+    const long per_chunk = long(std::max<size_t>(1, (kExpmBatchArenaBytes - 3*256)/one));
+    for (long at = 0; at < count; at += per_chunk) {
+        const size_t n = size_t(std::min(per_chunk, count - at));
+        StagedCall c;
+        const auto dK = c.in<double>(tiles + size_t(at)*rows*nn, n*rows*nn);
+        const auto dU = c.out<double>(n*nn);
+        const auto dFlags = c.out<int32_t>(n);
+        if (int rc = c.stage()) return rc;
+        if (int rc = ffk_expm_real_batch_dev(c[dK], long(n), rows, N, c[dU], c[dFlags], nullptr)) return rc;
+        if (int rc = c.copy_back(result + size_t(at)*nn, dU)) return rc;
+        if (int rc = c.copy_back(not_finite + at, dFlags)) return rc;
+        if (int rc = c.finish()) return rc;
+    }
+    return FFK_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 }  // extern "C"

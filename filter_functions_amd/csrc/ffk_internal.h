@@ -636,6 +636,14 @@ hipError_t launch_processes_decay(const cplx* const* Rtab, int P, int N, int W, 
 hipError_t launch_processes_expm(const double* K, int P, int rows, int N, double* out, int32_t* not_finite,
                                  hipStream_t stream);
 
+// ---- expm_batch.hip --------------------------------------------------------------------------
+// out (count, N, N) = exp(sum over the rows of tiles (count, rows, N, N)), 1 <= N <= 16, with the arithmetic plan of
+// launch_expm_real and the squarings chosen on the device, per matrix: one lane per matrix at N = 4, one wavefront
+// per matrix on the matrix cores else.  not_finite (count): 1 where the sum holds a NaN or Inf (nothing is written
+// for that matrix).  Launches only: no copy, no synchronisation, no workspace.
+hipError_t launch_expm_batch(const double* tiles, long count, int rows, int N, double* out, int32_t* not_finite,
+                             hipStream_t stream);
+
 // ---- generic.hip (17 <= d <= kMaxDGeneric) -----------------------------------------------------
 bool generic_dimension(int d);
 hipError_t launch_eigh_expm_generic(const cplx* H, const double* dt, int G, int d, double* eigvals,

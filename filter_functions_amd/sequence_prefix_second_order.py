@@ -21,7 +21,8 @@ from .batch import PASS_BYTES
 from .sequence_prefixes import (_closing_arrays, _products, sequence_prefix_decay_amplitudes, split_sequences)
 from .sequence_processes import MAX_CUMULANTS, _real_weights, stacked_spectra
 
-__all__ = ['sequence_prefix_frequency_shifts', 'sequence_prefix_cumulant_functions']
+__all__ = ['sequence_prefix_frequency_shifts', 'sequence_prefix_cumulant_functions',
+           'sequence_prefix_error_transfer_matrices']
 
 
 def block_width(d, A):
@@ -264,7 +265,8 @@ def sequence_prefix_cumulant_functions(gates, sequences, spectrum, omega, n_oper
     both apply --, and every tile goes through ``ffk_cumulant_function`` (and ``ffk_cumulant_function_second_order``)
     in chunks of what one launch takes, without a loop over the positions.  ``second_order=False`` runs no
     second-order code and gives the bits of the call without the keyword.  Gates of several bases evaluate the loop's
-    expression.  Error transfer matrices along a sequence are not offered."""
+    expression.  :func:`sequence_prefix_error_transfer_matrices` exponentiates the result of this call, every position
+    in one launch."""
     from .batch_second_order import _same_basis
     gates, sequences = list(gates), list(sequences)
     closing = None if closing is None else list(closing)
@@ -297,6 +299,45 @@ def sequence_prefix_cumulant_functions(gates, sequences, spectrum, omega, n_oper
     return (values, total) if want_U else values
 
 
-for _function in (sequence_prefix_frequency_shifts, sequence_prefix_cumulant_functions):
+def sequence_prefix_error_transfer_matrices(gates, sequences, spectrum, omega, n_oper_identifiers=None, closing=None,
+                                            second_order=False, stacked=False, return_propagators=False):
+    r"""Error transfer matrices :math:`\langle\tilde{\mathcal{U}}\rangle = \exp\mathcal{K}` along many sequences of
+    gates drawn from one gate set: a list of P arrays, entry p of shape (G_p, N, N), whose row m - 1 is
+
+    ``ff.error_transfer_matrix(pulse_m, spectrum, omega, n_oper_identifiers, second_order=second_order)``
+
+    with ``pulse_m`` the first m gates of sequence p (concatenated with ``calc_second_order_FF=True`` when
+    *second_order* is set): what tells depolarising from dephasing and a rotation from a contraction after every gate.
+    SHARED
+
+    A composition on the host: the cumulant functions come from :func:`sequence_prefix_cumulant_functions`, called
+    with the same arguments -- its routing, fallbacks, cache behaviour and same-bits properties all apply --, the
+    tiles of every position of every sequence under every spectrum are concatenated into one array, and that array
+    goes through :func:`ff.exponentiate_cumulant_functions
+    <filter_functions_amd.expm_batch.exponentiate_cumulant_functions>` once: the sum over the noise operators (over
+    both operator axes of a cross-spectrum, as the single function sums), the norm, the choice of the squarings and
+    the exponential of every position run in one launch per chunk, without a loop over the positions.  The values
+    agree with the loop's to rounding (the sums inside the matrix products are ordered differently from the single
+    function's); a position's matrix is the same bits alone or among others, stacked or one spectrum at a time, and
+    ``curve(s, closing)[:m]`` equals ``curve(s[:m], closing[:m])`` bit for bit.  Positions whose summed cumulant
+    function is not finite, complex cumulant functions and N > 16 evaluate the single function per position."""
+    from .expm_batch import exponentiate_cumulant_functions
+    want_U = bool(return_propagators)
+    first = sequence_prefix_cumulant_functions(gates, sequences, spectrum, omega, n_oper_identifiers,
+                                               closing=closing, second_order=second_order, stacked=stacked,
+                                               return_propagators=want_U)
+    cumulants, total = first if want_U else (first, None)
+    N = np.shape(cumulants[0])[-1]
+    lead = 2 if stacked else 1            # ([K,] G_p, operators ..., N, N): one matrix per leading index
+    heads = [np.shape(one)[:lead] for one in cumulants]
+    tiles = np.concatenate([np.reshape(one, (int(np.prod(head)), -1, N, N)) for one, head in zip(cumulants, heads)])
+    flat = exponentiate_cumulant_functions(tiles)
+    ends = np.cumsum([int(np.prod(head)) for head in heads])
+    values = [flat[end - int(np.prod(head)):end].reshape(tuple(head) + (N, N)) for head, end in zip(heads, ends)]
+    return (values, total) if want_U else values
+
+
+for _function in (sequence_prefix_frequency_shifts, sequence_prefix_cumulant_functions,
+                  sequence_prefix_error_transfer_matrices):
     _function.__doc__ = _function.__doc__.replace('\n    SHARED\n', _SHARED + '\n')
 del _function

@@ -455,6 +455,31 @@ size_t ffk_error_transfer_matrix_workspace_bytes(int N);
 int ffk_error_transfer_matrix_dev(const double* cumulant_function, int batch, int N, double* result,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- exp of MANY small matrices at once (ff.exponentiate_cumulant_functions, the error transfer matrices after
+ *      every gate of ff.sequence_prefix_error_transfer_matrices) ---------------------------------------------------
+ * tiles (count, rows, N, N) f64 row-major, 1 <= N <= 16 -> result (count, N, N) f64: matrix i is the sum of its
+ * `rows` tiles, added in order (as NumPy's sum over the leading axes), and result[i] its exponential by the plan of
+ * ffk_expm_real -- 1-norm, halvings until it is at most 1/2, Taylor polynomial of degree 18 (B^2, B^3, B^4 once, then
+ * Horner in B^4), squarings -- with the number of squarings chosen on the device, per matrix.  One launch whatever
+ * count: N = 4 runs one matrix per lane in registers, every other N one matrix per wavefront on v_mfma_f64_16x16x4.
+ * The sums inside the products are ordered differently from ffk_expm_real's, so the results are close to, not the
+ * bits of, that call; a matrix's result is the same bits at every count, at every place among the others and in
+ * every split.  not_finite (count,) int32: 1 where the sum holds a NaN or Inf -- that matrix's result tile is then not
+ * written --, else 0.
+ *   ffk_expm_real_batch_dev: device pointers; launches only -- no copy, no synchronisation, no allocation, no
+ *     workspace (unlike ffk_error_transfer_matrix_dev it is legal during stream capture).
+ *   ffk_expm_real_batch: host pointers; chunks of what the staging arena's budget of 1 GiB takes, each one H2D copy,
+ *     one launch and the D2H copies of its results and flags (a chunk's results come back whole: the HOST tile of a
+ *     flagged matrix holds no meaningful value afterwards).
+ *   ffk_expm_real_batch_workspace_bytes: the device bytes the host-pointer call stages for `count` matrices (tiles,
+ *     results, flags); needs no GPU; 0 for a shape that is not supported.
+ * NULL pointers, count < 0, rows < 1 and N outside [1, 16] are FFK_EINVAL before anything touches the device;
+ * count == 0 succeeds and does nothing.                                                                         */
+size_t ffk_expm_real_batch_workspace_bytes(long count, int rows, int N);
+int ffk_expm_real_batch_dev(const double* tiles, long count, int rows, int N, double* result, int32_t* not_finite,
+                            void* stream);
+int ffk_expm_real_batch(const double* tiles, long count, int rows, int N, double* result, int32_t* not_finite);
+
 /* ---- superoperator.liouville_representation (superoperator.py:51-84 + Basis.expand
  *      basis.py:350-371, 650-698) --------------------------------------------------------
  * U (batch, d, d) c128, basis (N, d, d) c128 -> liouville (batch, N, N):

@@ -2,10 +2,12 @@
 // R = tr(B~ C_k), filter function F = R^dag R and the trapezoid integrals of the infidelity.
 // All of these are single-pass, HBM-streaming kernels with omega as the fastest (lane) axis.
 #include <algorithm>
+#include <type_traits>
 
 #include <cstdlib>
 
 #include "ffk_internal.h"
+#include "ffk_mfma_util.h"
 
 namespace ffk {
 namespace {
@@ -496,6 +498,64 @@ __device__ __forceinline__ void infid_batch(int base, int W, const double* __res
     }
 }
 
+// infid_batch for the 256-thread block of infid_element, the running sums in the LDS slots `red`.  There the last
+// lane of a wavefront has no neighbour lane, and fetching integrand and frequency at w + 1 itself cost the wavefront
+// one more dependent trip to memory PER SLOT, sixteen a kernel at W = 4096 on top of the four of the batches.  But
+// w + 1 is the first lane's frequency in the next wavefront (same slot), or, for the block's last thread, thread 0's
+// in the next slot: the first lane of every wavefront leaves its four integrands and frequencies in `xch`
+// ([2][kInfidWaves][kInfidPer] doubles) and the last lanes read them after one barrier.  Only the block's very last
+// interval of a batch, which ends on the next batch's first frequency, is still fetched.  The integrand is the one
+// expression either way, and every slot gets the same terms in the same order: same bits.
+// xch is read while the next batch may already be under way in another wavefront: the caller alternates two of them.
+constexpr int kInfidWaves = kInfidThreads/64;
+constexpr int kInfidExchangeBytes = 2*2*kInfidWaves*kInfidPer*static_cast<int>(sizeof(double));
+template <typename LoadF, typename LoadS>
+__device__ __forceinline__ void infid_batch_block(int base, int W, const double* __restrict__ omega, LoadF Fat,
+                                                  LoadS Sat, double* red, double* xch) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (wave-uniform: a scalar register)
+    double i0[kInfidPer], om[kInfidPer];
+    {
+        cplx f[kInfidPer], sp[kInfidPer];
+#pragma unroll
+        for (int j = 0; j < kInfidPer; ++j) {
+            const int w = base + tid + kInfidThreads*j;
+            const int wc = w < W ? w : W - 1;
+            f[j] = Fat(wc);
+            sp[j] = Sat(wc);
+            om[j] = omega[wc];
+        }
+#pragma unroll
+        for (int j = 0; j < kInfidPer; ++j) i0[j] = f[j].re*sp[j].re - f[j].im*sp[j].im;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < kInfidPer; ++j) {
+            xch[wave*kInfidPer + j] = i0[j];
+            xch[kInfidWaves*kInfidPer + wave*kInfidPer + j] = om[j];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kInfidPer; ++j) {
+        const int w = base + tid + kInfidThreads*j;
+        double i1 = __shfl_down(i0[j], 1, 64), o1 = __shfl_down(om[j], 1, 64);
+        if (lane == 63) {
+            if (wave + 1 < kInfidWaves || j + 1 < kInfidPer) {
+                // thread tid + 1, slot j -- or thread 0, slot j + 1
+                const int nb = wave + 1 < kInfidWaves ? (wave + 1)*kInfidPer + j : j + 1;
+                i1 = xch[nb];
+                o1 = xch[kInfidWaves*kInfidPer + nb];
+            } else if (w + 1 < W) {
+                const cplx f1 = Fat(w + 1), s1 = Sat(w + 1);
+                i1 = f1.re*s1.re - f1.im*s1.im;
+                o1 = omega[w + 1];
+            }
+        }
+        if (w < W - 1) red[tid + kInfidThreads*j] += (i1 + i0[j])*(o1 - om[j]);
+    }
+}
+
 // The tree over the 1024 slots, pairing (v, v + s) for s = 512, 256, .., 1 as a loop over LDS with a barrier per level
 // would: the levels 512 and 256 pair slots of ONE thread (registers), 128 and 64 cross wavefronts (two barriers), the
 // last six stay inside wavefront 0 (lane shifts).  Same association, same bits, eight barriers fewer.
@@ -550,11 +610,15 @@ __device__ __forceinline__ void infid_element(const cplx* __restrict__ F, int A,
     auto Sat = [&](int w) -> cplx { return Sp[w]; };
     // this kernel runs beside another pass's accumulate blocks: 56 registers (tests/test_kernel_resources.py) -- the
     // running sums live in the LDS slots themselves (each thread its own four), the registers hold the loads in flight
+    extern __shared__ __attribute__((aligned(16))) unsigned char xch_raw[];      // kInfidExchangeBytes
+    double* xch = reinterpret_cast<double*>(xch_raw);
     double acc[kInfidPer];
 #pragma unroll
     for (int j = 0; j < kInfidPer; ++j) red[threadIdx.x + kInfidThreads*j] = 0.0;
+    int turn = 0;
     for (int base = 0; base < W - 1; base += kInfidSlots) {
-        infid_batch<0, kInfidPer>(base, W, omega, Fat, Sat, acc, red);
+        infid_batch_block(base, W, omega, Fat, Sat, red, xch + turn*2*kInfidWaves*kInfidPer);
+        turn ^= 1;
         asm volatile("" ::: "memory");      // (keeps the next batch's loads behind this batch's sums)
     }
     infid_finish<false>(red, acc, d, infid + p);
@@ -721,6 +785,21 @@ __global__ __launch_bounds__(64) void expand_chunks_kernel(const cplx* __restric
 // The same expansion followed, in the same launch, by the fidelity filter function of the block's
 // 16 frequencies: F[a,b,w] = sum_k conj(R[a,k,w]) R[b,k,w] (a <= b, mirrored; the summation order
 // of ff_fidelity_kernel).  Block = 16 frequencies x `kt` basis-element lanes; R passes through LDS.
+// The compacted basis (nnz, rows, vals) is the same for every block and every noise operator.  Where it is small
+// (d <= 4: 4.3 KiB with the rows as bytes) each block copies it into LDS once, at the top and together with the
+// partial sums' loads, instead of fetching counts, rows and values from memory in a dependent chain behind the
+// barrier, once per operator.  The cap keeps two blocks of config 2 (24 KiB of tiles each) beside an accumulate
+// block of another pass (pq_lds_bytes_for(3) = 102752 B of the CU's 160 KiB, whatever the allocation granule).
+constexpr int kExpandListCap = 4608;
+__host__ __device__ inline int expand_ff_list_bytes(int N, int dd) {
+    if (dd > 256) return 0;                             // (rows as bytes)
+    const long n = static_cast<long>(N)*dd;
+    const long bytes = n*static_cast<long>(sizeof(cplx)) + ((n + 15) & ~15L) + ((2L*N + 15) & ~15L);
+    return bytes <= kExpandListCap ? static_cast<int>(bytes) : 0;
+}
+// partial sums a thread has in flight at a time (two rounds of config 2's 3 entries x 4 chunks)
+constexpr int kExpandLoads = 6;
+
 // (one pulse's partial sums; the kernels below pick the pulse)
 __device__ __forceinline__ void expand_ff_tile(const cplx* __restrict__ Ypart, int chunks, size_t slab,
                                                const int* __restrict__ nnz, const int* __restrict__ rows,
@@ -736,38 +815,99 @@ __device__ __forceinline__ void expand_ff_tile(const cplx* __restrict__ Ypart, i
     const int at = (blockDim.x >> 4) / kt;
     const int w = blockIdx.x*16 + wl;
     const int wc = w < W ? w : W - 1;
+    // the basis lists in LDS (expand_ff_list_bytes != 0): values by LDS-DMA, rows and counts through one register each
+    const int nlist = N*dd;
+    const bool lists = expand_ff_list_bytes(N, dd) != 0;
+    cplx* vl = ys + static_cast<size_t>(A)*dd*16;                                   // [N*dd]
+    unsigned char* rows8 = reinterpret_cast<unsigned char*>(vl + nlist);            // [N*dd]
+    unsigned short* nl = reinterpret_cast<unsigned short*>(rows8 + ((nlist + 15) & ~15));    // [N]
+    const int tid = threadIdx.x, nthreads = blockDim.x;
+    int row_first = 0, nnz_first = 0;
+    if (lists) {
+        for (int e0 = tid & ~63; e0 < nlist; e0 += nthreads)
+            if (e0 + (tid & 63) < nlist) lds_dma16(vals + e0 + (tid & 63), vl + e0);
+        row_first = rows[min(tid, nlist - 1)];          // (threads past the end: a clamped index, value unused)
+        nnz_first = nnz[min(tid, N - 1)];
+    }
     // every partial sum is read from memory once (in chunk order) and expanded from LDS: a matrix
-    // element takes part in several basis elements (four for the Pauli basis of d = 4)
-    for (int idx = threadIdx.x >> 4; idx < A*dd; idx += blockDim.x >> 4) {
-        const cplx* b = Ypart + static_cast<size_t>(idx)*W + wc;
-        cplx acc = b[0];
-        for (int z = 1; z < chunks; ++z) {
-            const cplx v = b[z*slab];
-            acc.re += v.re;
-            acc.im += v.im;
+    // element takes part in several basis elements (four for the Pauli basis of d = 4).  The (entry, chunk) pairs
+    // of a thread, entry-major, go in rounds of kExpandLoads loads that are all issued before the round's first
+    // sum; the sums run in the order of the pairs: every entry's chunks in chunk order, as one loop per entry did.
+    {
+        const int lanes = nthreads >> 4, lane0 = tid >> 4;
+        const int entries = lane0 < A*dd ? (A*dd - lane0 + lanes - 1)/lanes : 0;
+        const int total = entries*chunks;
+        int il = 0, zl = 0;                             // entry and chunk of the next load ...
+        int is = 0, zs = 0;                             // ... and of the next sum
+        double acc_re = 0.0, acc_im = 0.0;
+        for (int t0 = 0; t0 < total; t0 += kExpandLoads) {
+            double vr[kExpandLoads], vi[kExpandLoads];
+#pragma unroll
+            for (int u = 0; u < kExpandLoads; ++u) {
+                // (past the thread's last pair: the last pair again, value unused)
+                const cplx* from = Ypart + static_cast<size_t>(lane0 + il*lanes)*W + wc + zl*slab;
+                vr[u] = from->re;
+                vi[u] = from->im;
+                if (t0 + u + 1 < total && ++zl == chunks) {
+                    zl = 0;
+                    ++il;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kExpandLoads; ++u) {
+                if (t0 + u < total) {
+                    if (zs == 0) {
+                        acc_re = vr[u];
+                        acc_im = vi[u];
+                    } else {
+                        acc_re += vr[u];
+                        acc_im += vi[u];
+                    }
+                    if (++zs == chunks) {
+                        ys[static_cast<size_t>(lane0 + is*lanes)*16 + wl] = {acc_re, acc_im};
+                        zs = 0;
+                        ++is;
+                    }
+                }
+            }
         }
-        ys[static_cast<size_t>(idx)*16 + wl] = acc;
+    }
+    if (lists) {
+        if (tid < nlist) rows8[tid] = static_cast<unsigned char>(row_first);
+        if (tid < N) nl[tid] = static_cast<unsigned short>(nnz_first);
+        for (int i = tid + nthreads; i < nlist; i += nthreads) rows8[i] = static_cast<unsigned char>(rows[i]);
+        for (int i = tid + nthreads; i < N; i += nthreads) nl[i] = static_cast<unsigned short>(nnz[i]);
+        lds_dma_wait();
     }
     __syncthreads();
-    for (int a = al; a < A; a += at) {
-        const cplx* ya = ys + static_cast<size_t>(a)*dd*16 + wl;
-        for (int k = kl; k < N; k += kt) {
-            const int n = nnz[k];
-            const int* rk = rows + static_cast<size_t>(k)*dd;
-            const cplx* vk = vals + static_cast<size_t>(k)*dd;
-            auto summed = [&](int e) { return ya[e*16]; };
-            cplx acc0 = {0.0, 0.0}, acc1 = {0.0, 0.0};
-            int q = 0;
-            for (; q + 1 < n; q += 2) {
-                cmac(acc0, vk[q], summed(rk[q]));
-                cmac(acc1, vk[q + 1], summed(rk[q + 1]));
+    // (the two sources of the lists as two loop nests: one nest with a branch inside held both sources' addresses in
+    // registers, two over the 56 the kernel has beside an accumulate block)
+    auto expand = [&](auto from_lds) {
+        for (int a = al; a < A; a += at) {
+            const cplx* ya = ys + static_cast<size_t>(a)*dd*16 + wl;
+            for (int k = kl; k < N; k += kt) {
+                auto summed = [&](int e) { return ya[e*16]; };
+                cplx acc0 = {0.0, 0.0}, acc1 = {0.0, 0.0};
+                auto contract = [&](int n, auto rk, const cplx* vk) {
+                    int q = 0;
+                    for (; q + 1 < n; q += 2) {
+                        cmac(acc0, vk[q], summed(rk[q]));
+                        cmac(acc1, vk[q + 1], summed(rk[q + 1]));
+                    }
+                    if (q < n) cmac(acc0, vk[q], summed(rk[q]));
+                };
+                if constexpr (decltype(from_lds)::value)
+                    contract(nl[k], rows8 + static_cast<size_t>(k)*dd, vl + static_cast<size_t>(k)*dd);
+                else
+                    contract(nnz[k], rows + static_cast<size_t>(k)*dd, vals + static_cast<size_t>(k)*dd);
+                const cplx r = {acc0.re + acc1.re, acc0.im + acc1.im};
+                rl[(static_cast<size_t>(a)*N + k)*16 + wl] = r;
+                if (w < W) R[(static_cast<size_t>(a)*N + k)*W + w] = r;
             }
-            if (q < n) cmac(acc0, vk[q], summed(rk[q]));
-            const cplx r = {acc0.re + acc1.re, acc0.im + acc1.im};
-            rl[(static_cast<size_t>(a)*N + k)*16 + wl] = r;
-            if (w < W) R[(static_cast<size_t>(a)*N + k)*W + w] = r;
         }
-    }
+    };
+    if (lists) expand(std::true_type{});
+    else expand(std::false_type{});
     __syncthreads();
     if (w >= W) return;
     const int npairs = A*(A + 1)/2;
@@ -826,7 +966,7 @@ hipError_t launch_expand_ff(const cplx* Ypart, int chunks, size_t slab, int A, i
     // do not) and then waits for that whole kernel -- with the front of the next-but-one pass queued
     // behind it on the same stream
     const int at = std::max(1, std::min(A, 16/kt));
-    const size_t lds = static_cast<size_t>(A)*(N + d*d)*16*sizeof(cplx);
+    const size_t lds = static_cast<size_t>(A)*(N + d*d)*16*sizeof(cplx) + expand_ff_list_bytes(N, d*d);
     if (lds > 160*1024) return hipErrorInvalidValue;
     if (lds > 48*1024) {
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(expand_ff_kernel),
@@ -845,7 +985,7 @@ hipError_t launch_expand_ff_pulses(const cplx* Ypart, int chunks, size_t slab, i
     const CompactWs cw = slice_compact_ws(ws, N, d);
     const int kt = N >= 16 ? 16 : (N >= 8 ? 8 : 4);
     const int at = std::max(1, std::min(A, 16/kt));
-    const size_t lds = static_cast<size_t>(A)*(N + d*d)*16*sizeof(cplx);
+    const size_t lds = static_cast<size_t>(A)*(N + d*d)*16*sizeof(cplx) + expand_ff_list_bytes(N, d*d);
     if (lds > 160*1024) return hipErrorInvalidValue;
     if (lds > 48*1024) {
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(expand_ff_pulses_kernel),
@@ -1041,8 +1181,8 @@ hipError_t launch_infidelity_pulses(const cplx* F, int A, int W, int P, const cp
                                     hipStream_t stream) {
     const int nout = s_ndim == 3 ? n_idx*n_idx : n_idx;
     if (P < 1 || P > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(infid_pulses_kernel, dim3(nout, P), dim3(kInfidThreads), 0, stream, F, A, W, S, s_ndim,
-                       omega, idx, n_idx, d, nout, infid);
+    hipLaunchKernelGGL(infid_pulses_kernel, dim3(nout, P), dim3(kInfidThreads), kInfidExchangeBytes, stream, F, A, W, S,
+                       s_ndim, omega, idx, n_idx, d, nout, infid);
     return hipGetLastError();
 }
 
@@ -1063,10 +1203,12 @@ hipError_t launch_infidelity(const cplx* F, int A, int W, const cplx* S, int s_n
     }
     // (one shard as wide as the grid -- the single-GPU bench -- IS the plain layout: no index division per load)
     if (shard_width > 0 && shard_width < W)
-        hipLaunchKernelGGL(infid_kernel<true>, dim3(nout), dim3(kInfidThreads), 0, stream, F, A, W, S, s_ndim, omega,
+        hipLaunchKernelGGL(infid_kernel<true>, dim3(nout), dim3(kInfidThreads), kInfidExchangeBytes, stream, F, A, W, S,
+                           s_ndim, omega,
                            idx, n_idx, d, shard_width, infid);
     else
-        hipLaunchKernelGGL(infid_kernel<false>, dim3(nout), dim3(kInfidThreads), 0, stream, F, A, W, S, s_ndim, omega,
+        hipLaunchKernelGGL(infid_kernel<false>, dim3(nout), dim3(kInfidThreads), kInfidExchangeBytes, stream, F, A, W, S,
+                           s_ndim, omega,
                            idx, n_idx, d, shard_width, infid);
     return hipGetLastError();
 }

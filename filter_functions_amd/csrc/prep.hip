@@ -8,33 +8,101 @@
 // packed per segment as ops[g] = (T_g, Bbar_0^(g), ..., Bbar_{A-1}^(g)), the block of operands the
 // accumulate kernel stages in LDS for segment g.
 #include "ffk_internal.h"
+#include "ffk_mfma_util.h"
 
 namespace ffk {
 namespace {
 
-// Prologue arithmetic for one segment by one wavefront; V (eigenvectors) and Q (propagator
-// before the segment) already sit in LDS.
+// The prologue of one segment by one wavefront, in two halves around the propagator Q_g:
+//   prologue_front  everything that needs only the eigensystem: the table row (dE, sin/cos of b, the threshold) and
+//                   Bbar_a = s V^dag B_a V of every operator;
+//   prologue_back   what needs Q_g: T = V^dag Q, Tc, the T block of ops, and (d = 4) the fold of the accumulate
+//                   kernel's operand W_a.
+// What either half reads from memory is asked for at the top of the block, in one go and before the first wait
+// (prologue_front_loads; the fused kernel below adds the chunk totals and its two propagators): one trip to memory
+// instead of one per array.  The matrices go straight into LDS (lds_dma16: no register holds them while they are on
+// their way -- the kernel runs beside another pass's accumulate blocks on 56 registers); a lane's scalars wait in
+// registers.  The products and sums are the ones the one-piece prologue made, operand by operand: the same bits.
+// d <= 8 (one entry of a d x d matrix per lane); larger d reads everything where it is used, as ever.
 template <int D>
-__device__ void prologue_segment(const cplx (*V)[D], cplx (*Q)[D], cplx (*T)[D], cplx (*BV)[D],
-                                 int g, int lane, const double* __restrict__ eigvals,
-                                 const cplx* __restrict__ n_opers,
-                                 const double* __restrict__ n_coeffs,
-                                 const double* __restrict__ dt, const double* __restrict__ t, int G,
-                                 int A, double* __restrict__ segtab, cplx* __restrict__ Tc,
-                                 cplx* __restrict__ ops, cplx* __restrict__ n_opers_transformed,
-                                 cplx* __restrict__ eigvecs_propagated, bool with_noise_ops = true,
-                                 cplx* __restrict__ wfold = nullptr) {
+constexpr bool kOneEntryPerLane = D*D <= 64;
+// Operators per pass of the 64 lanes (d <= 8: lane = (operator q of the pass, entry e), like the prefix tree's
+// products; larger d: one operator, several entries per lane) -- at d = 4 the B and the coefficients of up to four
+// operators come in ONE trip to memory, and the two products take one pair of barriers for all of them.
+template <int D>
+constexpr int kOpsPerPass = D*D <= 64 ? 64/(D*D) : 1;
+
+// The fold of the d = 4 operand needs every Bbar_a again once T is known.  Up to one pass of operators (four) they
+// wait in LDS, in the place of the B they were made from (Bl is free once B V is out); with more operators each lane
+// reads its entries back from `ops`.  No array of their own: with 2 KiB more the block was 10 KiB of LDS, and the
+// kernel's launches beside another pass's accumulate blocks took 12.7 us on average instead of 9.9 (up to 48: blocks
+// waiting for an accumulate block to retire), although a launch on its own was 2 us shorter.
+template <int D>
+__device__ __forceinline__ int bbar_kept(int A) { return A <= kOpsPerPass<D> ? A : 0; }
+
+template <int D>
+struct PrologueLoads {
+    double em, en;                                  // D_m, D_n of the lane's entry (m, n)
+    double dtg, tg;
+    double s;                                       // coefficient of the lane's operator of the first pass
+};
+
+// B of the operators [a0, a0 + kOpsPerPass) into Bl by LDS-DMA, the lane's operator's coefficient for segment g
+// into s (kOneEntryPerLane; lanes past the last operator: a clamped index, value unused).  The caller waits
+// (lds_dma_wait) and synchronises before Bl is read.
+template <int D>
+__device__ __forceinline__ void operator_pass_loads(double& s, cplx (*Bl)[D][D], int a0, int lane,
+                                                    const cplx* __restrict__ n_opers,
+                                                    const double* __restrict__ n_coeffs, int G, int A, int g) {
+    constexpr int DD = D*D, PER = kOpsPerPass<D>;
+    if (lane < min(PER, A - a0)*DD) lds_dma16(n_opers + static_cast<size_t>(a0)*DD + lane, &Bl[0][0][0]);
+    const int a = min(a0 + min(lane / DD, PER - 1), A - 1);
+    s = n_coeffs ? n_coeffs[static_cast<size_t>(a)*G + g] : 1.0;   // NULL: unit
+}
+
+template <int D>
+__device__ __forceinline__ void prologue_front_loads(PrologueLoads<D>& ld, cplx (*Bl)[D][D], int g, int lane,
+                                                     const double* __restrict__ eigvals,
+                                                     const double* __restrict__ dt, const double* __restrict__ t,
+                                                     const cplx* __restrict__ n_opers,
+                                                     const double* __restrict__ n_coeffs, int G, int A,
+                                                     bool with_noise_ops) {
+    const int e = min(lane, D*D - 1);                 // (lanes past the matrix: a clamped index, value unused)
+    ld.em = eigvals[static_cast<size_t>(g)*D + e / D];
+    ld.en = eigvals[static_cast<size_t>(g)*D + e % D];
+    ld.dtg = dt[g];
+    ld.tg = t[g];
+    ld.s = 1.0;
+    if constexpr (kOneEntryPerLane<D>) {
+        if (with_noise_ops && A > 0) operator_pass_loads<D>(ld.s, Bl, 0, lane, n_opers, n_coeffs, G, A, g);
+    }
+}
+
+// V and, for d <= 8, Bl (the first pass's operators) and ld are in place (prologue_front_loads, waited for and
+// synchronised).  Bl, BV: [kOpsPerPass][D][D]; Bbar of the operators below bbar_kept stays in Bl.  Returns e^{i b_mn}
+// of this lane's entry (d = 4: one entry per lane < 16).
+template <int D>
+__device__ __forceinline__ cplx prologue_front(const cplx (*V)[D], cplx (*Bl)[D][D], cplx (*BV)[D][D],
+                                               int g, int lane, const PrologueLoads<D>& ld,
+                                               const double* __restrict__ eigvals, const cplx* __restrict__ n_opers,
+                                               const double* __restrict__ n_coeffs, int G, int A,
+                                               double* __restrict__ segtab, cplx* __restrict__ ops,
+                                               cplx* __restrict__ n_opers_transformed, bool with_noise_ops,
+                                               bool fold) {
     constexpr int S = seg_stride(D);
+    constexpr int DD = D*D, PER = kOpsPerPass<D>;
     double* st = segtab + static_cast<size_t>(g)*S;
     if (lane == 0) {
-        st[0] = dt[g];
-        st[1] = t[g];
+        st[0] = ld.dtg;
+        st[1] = ld.tg;
     }
-    cplx eb = {1.0, 0.0};                              // e^{i b_mn} of this lane's entry (d = 4: one entry per lane < 16)
-    for (int e = lane; e < D*D; e += 64) {
-        const double dE = eigvals[static_cast<size_t>(g)*D + e / D] - eigvals[static_cast<size_t>(g)*D + e % D];
+    cplx eb = {1.0, 0.0};                              // e^{i b_mn} of this lane's entry
+    for (int e = lane; e < DD; e += 64) {
+        double dE;
+        if constexpr (kOneEntryPerLane<D>) dE = ld.em - ld.en;
+        else dE = eigvals[static_cast<size_t>(g)*D + e / D] - eigvals[static_cast<size_t>(g)*D + e % D];
         double sb, cb;
-        sincos_pi(0.5*(dE*dt[g]), &sb, &cb);
+        sincos_pi(0.5*(dE*ld.dtg), &sb, &cb);
         st[seg_rec(e)] = dE;
         st[seg_rec(e) + 1] = sb;
         st[seg_rec(e) + 2] = cb;
@@ -43,10 +111,68 @@ __device__ void prologue_segment(const cplx (*V)[D], cplx (*Q)[D], cplx (*T)[D],
     }
     // [2]: the near-resonance threshold 2^-4/dt_g, phased_frequency()'s own expression (the d = 4 producers read
     // it with the head record instead of forming it per tile and lane, ctrl_pq.hip)
-    if (lane == 0) st[2] = dt[g] > 0.0 ? 0.0625*rcp(dt[g]) : __builtin_huge_val();
+    if (lane == 0) st[2] = ld.dtg > 0.0 ? 0.0625*rcp(ld.dtg) : __builtin_huge_val();
     if (lane == 1) st[3] = 0.0;
-    for (int e = 4 + 4*D*D + lane; e < S; e += 64) st[e] = 0.0;
+    for (int e = 4 + 4*DD + lane; e < S; e += 64) st[e] = 0.0;
 
+    if (!with_noise_ops) return eb;     // (large d: noise_ops_kernel, one block per operator)
+    // Bbar = s V^dag BV, entry e of operator a (q: its place in the pass)
+    auto bbar_entry = [&](int a, int q, int e, double s) {
+        const int m = e / D, n = e % D;
+        cplx acc = {0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < D; ++k) cmac_conj(acc, V[k][m], BV[q][k][n]);
+        acc.re *= s;
+        acc.im *= s;
+        ops[(static_cast<size_t>(g)*(1 + A) + 1 + a)*DD + e] = acc;
+        if (n_opers_transformed)
+            n_opers_transformed[(static_cast<size_t>(a)*G + g)*DD + e] = acc;
+        if (fold && a < bbar_kept<D>(A)) Bl[a][m][n] = acc;     // (one pass: a = q, and B V of the pass is out)
+    };
+    double s = ld.s;
+    for (int a0 = 0; a0 < A; a0 += PER) {
+        if constexpr (kOneEntryPerLane<D>) {
+            if (a0 > 0) {
+                // (every lane has its products of the pass before out of Bl: the barrier that ended it)
+                operator_pass_loads<D>(s, Bl, a0, lane, n_opers, n_coeffs, G, A, g);
+                lds_dma_wait();
+                __syncthreads();
+            }
+            const int q = lane / DD, e = lane % DD, i = e / D, n = e % D;
+            const bool act = q < PER && a0 + q < A;
+            if (act) {                                  // BV = B V
+                cplx acc = {0.0, 0.0};
+#pragma unroll
+                for (int k = 0; k < D; ++k) cmac(acc, Bl[q][i][k], V[k][n]);
+                BV[q][i][n] = acc;
+            }
+            __syncthreads();
+            if (act) bbar_entry(a0 + q, q, e, s);
+            __syncthreads();
+        } else {
+            const cplx* B = n_opers + static_cast<size_t>(a0)*DD;
+            s = n_coeffs ? n_coeffs[static_cast<size_t>(a0)*G + g] : 1.0;   // NULL: unit
+            for (int e = lane; e < DD; e += 64) {       // BV = B V
+                const int i = e / D, n = e % D;
+                cplx acc = {0.0, 0.0};
+#pragma unroll
+                for (int k = 0; k < D; ++k) cmac(acc, B[i*D + k], V[k][n]);
+                BV[0][i][n] = acc;
+            }
+            __syncthreads();
+            for (int e = lane; e < DD; e += 64) bbar_entry(a0, 0, e, s);
+            __syncthreads();
+        }
+    }
+    return eb;
+}
+
+template <int D>
+__device__ __forceinline__ void prologue_back(const cplx (*V)[D], cplx (*Q)[D], cplx (*T)[D], cplx (*BV)[D][D],
+                                              const cplx (*Bl)[D][D], cplx eb, int g, int lane, int A,
+                                              cplx* __restrict__ Tc, cplx* __restrict__ ops,
+                                              cplx* __restrict__ eigvecs_propagated, bool fold,
+                                              cplx* __restrict__ wfold) {
     // T = V^dag Q
     for (int e = lane; e < D*D; e += 64) {
         const int m = e / D, j = e % D;
@@ -61,55 +187,58 @@ __device__ void prologue_segment(const cplx (*V)[D], cplx (*Q)[D], cplx (*T)[D],
             eigvecs_propagated[static_cast<size_t>(g)*D*D + j*D + m] = {acc.re, -acc.im};
     }
     __syncthreads();
-
-    if (!with_noise_ops) return;        // (large d: noise_ops_kernel, one block per operator)
     // d = 4 with a buffer for it (ffk_internal.h wfold): W_a[n][m][j] = Bbar_a[m][n] e^{i b_mn} T[n][j], the
     // operand the accumulate kernel's tiles hold, folded here once per segment.  Q is free by now: it keeps e^{ib}.
-    const bool fold = D == 4 && wfold != nullptr;
-    if (fold) {
+    if constexpr (D == 4) {
+        if (!fold) return;
         if (lane < D*D) Q[lane / D][lane % D] = eb;
         __syncthreads();
-    }
-    for (int a = 0; a < A; ++a) {
-        const cplx* B = n_opers + static_cast<size_t>(a)*D*D;
-        const double s = n_coeffs ? n_coeffs[static_cast<size_t>(a)*G + g] : 1.0;   // NULL: unit
-        // BV = B V
-        for (int e = lane; e < D*D; e += 64) {
-            const int i = e / D, n = e % D;
-            cplx acc = {0.0, 0.0};
-#pragma unroll
-            for (int k = 0; k < D; ++k) cmac(acc, B[i*D + k], V[k][n]);
-            BV[i][n] = acc;
-        }
-        __syncthreads();
-        // Bbar = s V^dag BV
-        cplx bbar = {0.0, 0.0};
-        for (int e = lane; e < D*D; e += 64) {
-            const int m = e / D, n = e % D;
-            cplx acc = {0.0, 0.0};
-#pragma unroll
-            for (int k = 0; k < D; ++k) cmac_conj(acc, V[k][m], BV[k][n]);
-            acc.re *= s;
-            acc.im *= s;
-            ops[(static_cast<size_t>(g)*(1 + A) + 1 + a)*D*D + e] = acc;
-            if (n_opers_transformed)
-                n_opers_transformed[(static_cast<size_t>(a)*G + g)*D*D + e] = acc;
-            if (fold) bbar = acc;
-        }
-        __syncthreads();
-        if (fold) {
-            if (lane < D*D) BV[lane / D][lane % D] = bbar;      // (every lane has its products out of BV: the barrier above)
-            __syncthreads();
-            if constexpr (D == 4) {
-                // lane = (m, n, j), the accumulate kernel's order of products: (e^{ib} T) first, then Bbar times that
-                const int m = lane >> 4, n = (lane >> 2) & 3, j = lane & 3;
-                const cplx et = cmul(Q[m][n], T[n][j]);
-                const cplx w = cmul(BV[m][n], et);
-                wfold[(static_cast<size_t>(g)*A + a)*64 + n*16 + m*4 + j] = w;
+        // lane = (m, n, j), the accumulate kernel's order of products: (e^{ib} T) first, then Bbar times that
+        const int m = lane >> 4, n = (lane >> 2) & 3, j = lane & 3;
+        const cplx et = cmul(Q[m][n], T[n][j]);
+        for (int a = 0; a < A; ++a) {
+            const bool kept = a < bbar_kept<D>(A);
+            const cplx* bbar = &Bl[kept ? a : 0][m][n];
+            if (!kept) {
+                // (each lane reads back the entry of Bbar_a that it wrote itself: prologue_front's lane (q, e))
+                if (lane / (D*D) == a % kOpsPerPass<D>) {
+                    const int e = lane % (D*D);
+                    BV[0][e / D][e % D] = ops[(static_cast<size_t>(g)*(1 + A) + 1 + a)*D*D + e];
+                }
+                __syncthreads();
+                bbar = &BV[0][m][n];
             }
-            __syncthreads();
+            const cplx w = cmul(*bbar, et);
+            wfold[(static_cast<size_t>(g)*A + a)*64 + n*16 + m*4 + j] = w;
+            if (!kept) __syncthreads();
         }
     }
+}
+
+// Prologue arithmetic for one segment by one wavefront; V (eigenvectors) and Q (propagator
+// before the segment) already sit in LDS.
+template <int D>
+__device__ void prologue_segment(const cplx (*V)[D], cplx (*Q)[D], cplx (*T)[D],
+                                 int g, int lane, const double* __restrict__ eigvals,
+                                 const cplx* __restrict__ n_opers,
+                                 const double* __restrict__ n_coeffs,
+                                 const double* __restrict__ dt, const double* __restrict__ t, int G,
+                                 int A, double* __restrict__ segtab, cplx* __restrict__ Tc,
+                                 cplx* __restrict__ ops, cplx* __restrict__ n_opers_transformed,
+                                 cplx* __restrict__ eigvecs_propagated, bool with_noise_ops = true,
+                                 cplx* __restrict__ wfold = nullptr) {
+    __shared__ __attribute__((aligned(16))) cplx Bl[kOpsPerPass<D>][D][D];
+    __shared__ cplx BV[kOpsPerPass<D>][D][D];
+    const bool fold = D == 4 && wfold != nullptr && with_noise_ops;
+    PrologueLoads<D> ld;
+    prologue_front_loads<D>(ld, Bl, g, lane, eigvals, dt, t, n_opers, n_coeffs, G, A, with_noise_ops);
+    if constexpr (kOneEntryPerLane<D>) {
+        lds_dma_wait();
+        __syncthreads();
+    }
+    const cplx eb = prologue_front<D>(V, Bl, BV, g, lane, ld, eigvals, n_opers, n_coeffs, G, A, segtab, ops,
+                                      n_opers_transformed, with_noise_ops, fold);
+    prologue_back<D>(V, Q, T, BV, Bl, eb, g, lane, A, Tc, ops, eigvecs_propagated, fold, wfold);
 }
 
 template <int D>
@@ -123,7 +252,6 @@ __global__ __launch_bounds__(64) void prologue_kernel(
     __shared__ cplx V[D][D];
     __shared__ cplx Q[D][D];
     __shared__ cplx T[D][D];
-    __shared__ cplx BV[D][D];
     const int g = blockIdx.x;
     const int lane = threadIdx.x;
     for (int e = lane; e < D*D; e += 64) {
@@ -131,7 +259,7 @@ __global__ __launch_bounds__(64) void prologue_kernel(
         Q[e / D][e % D] = propagators[static_cast<size_t>(g)*D*D + e];
     }
     __syncthreads();
-    prologue_segment<D>(V, Q, T, BV, g, lane, eigvals, n_opers, n_coeffs, dt, t, G, A, segtab, Tc,
+    prologue_segment<D>(V, Q, T, g, lane, eigvals, n_opers, n_coeffs, dt, t, G, A, segtab, Tc,
                         ops, n_opers_transformed, eigvecs_propagated, with_noise_ops, wfold);
 }
 
@@ -146,7 +274,6 @@ __global__ __launch_bounds__(64) void prologue_pulses_kernel(
     __shared__ cplx V[D][D];
     __shared__ cplx Q[D][D];
     __shared__ cplx T[D][D];
-    __shared__ cplx BV[D][D];
     constexpr size_t DD = D*D;
     const size_t p = blockIdx.y;
     const int g = blockIdx.x;
@@ -158,7 +285,7 @@ __global__ __launch_bounds__(64) void prologue_pulses_kernel(
         Q[e / D][e % D] = Qp[static_cast<size_t>(g)*DD + e];
     }
     __syncthreads();
-    prologue_segment<D>(V, Q, T, BV, g, lane, eigvals + p*G*D, n_opers + p*A*DD, n_coeffs + p*A*G, dt + p*G,
+    prologue_segment<D>(V, Q, T, g, lane, eigvals + p*G*D, n_opers + p*A*DD, n_coeffs + p*A*G, dt + p*G,
                         t + p*(G + 1), G, A, segtab + p*G*seg_stride(D), Tc + p*G*DD, ops + p*G*(1 + A)*DD,
                         n_opers_transformed + p*A*G*DD, nullptr, true, nullptr);
 }
@@ -220,11 +347,13 @@ __device__ __forceinline__ void apply_prologue_segment(
     bool with_noise_ops, cplx* __restrict__ wfold, const int g) {
     __builtin_amdgcn_s_setprio(3);     // see ffk_internal.h FFK_SMALL_KERNEL_PRIORITY
     __shared__ cplx E[2][D][D];
-    __shared__ cplx M[D][D];
-    __shared__ cplx V[D][D];
+    __shared__ __attribute__((aligned(16))) cplx M[D][D];      // Qloc[g+1]
+    __shared__ __attribute__((aligned(16))) cplx Mg[D][D];     // Qloc[g]
+    __shared__ __attribute__((aligned(16))) cplx V[D][D];
+    __shared__ __attribute__((aligned(16))) cplx Bl[kOpsPerPass<D>][D][D];
     __shared__ cplx Q[D][D];
     __shared__ cplx T[D][D];
-    __shared__ cplx BV[D][D];
+    __shared__ cplx BV[kOpsPerPass<D>][D][D];
     constexpr int kBatch = 16;
     constexpr bool kTree = D <= 8;                 // a whole matrix fits one pass of the 64 lanes
     // the chunk totals: for the tree as many as the launch has chunks (dynamic LDS: 4 KiB at config 2;
@@ -235,17 +364,50 @@ __device__ __forceinline__ void apply_prologue_segment(
     cplx (*tot)[D][D] = reinterpret_cast<cplx (*)[D][D]>(tot_raw);
     const int lane = threadIdx.x;
     const int c = g / L;
-    for (int e = lane; e < D*D; e += 64) E[0][e / D][e % D] = {(e / D == e % D) ? 1.0 : 0.0, 0.0};
+    const bool prologue = segtab != nullptr;       // (nullptr: the scan fix-up alone)
+    const bool fold = D == 4 && wfold != nullptr && with_noise_ops;
+    // Every load of the block is issued here, before the first wait (d <= 8; see prologue_front): the matrices by
+    // LDS-DMA -- eigenvectors, the first operators, the two local propagators, the chunk totals (lanes past an array's
+    // end copy nothing) --, the lane's scalars into registers.
+    constexpr int DD = D*D;
+    PrologueLoads<D> ld;
+    if constexpr (kOneEntryPerLane<D>) {
+        if (prologue) {
+            prologue_front_loads<D>(ld, Bl, g, lane, eigvals, dt, t, n_opers, n_coeffs, G, A, with_noise_ops);
+            if (lane < DD) lds_dma16(eigvecs + static_cast<size_t>(g)*DD + lane, &V[0][0]);
+        }
+        if (lane < DD) {
+            lds_dma16(Qloc + static_cast<size_t>(g + 1)*DD + lane, &M[0][0]);
+            // (unused where g opens a chunk: Q_g is the prefix itself)
+            lds_dma16(Qloc + static_cast<size_t>(g)*DD + lane, &Mg[0][0]);
+        }
+        for (int e0 = 0; e0 < c*DD; e0 += 64)
+            if (e0 + lane < c*DD) lds_dma16(totals + e0 + lane, &tot[0][0][0] + e0);
+        lds_dma_wait();
+    } else {
+        if (prologue) {
+            prologue_front_loads<D>(ld, Bl, g, lane, eigvals, dt, t, n_opers, n_coeffs, G, A, with_noise_ops);
+            for (int e = lane; e < DD; e += 64) V[e / D][e % D] = eigvecs[static_cast<size_t>(g)*DD + e];
+        }
+        for (int e = lane; e < DD; e += 64) {
+            M[e / D][e % D] = Qloc[static_cast<size_t>(g + 1)*DD + e];
+            Mg[e / D][e % D] = Qloc[static_cast<size_t>(g)*DD + e];
+        }
+    }
+    for (int e = lane; e < DD; e += 64) E[0][e / D][e % D] = {(e / D == e % D) ? 1.0 : 0.0, 0.0};
+    __syncthreads();
+    cplx eb = {1.0, 0.0};
+    if (prologue)
+        eb = prologue_front<D>(V, Bl, BV, g, lane, ld, eigvals, n_opers, n_coeffs, G, A, segtab, ops, nullptr,
+                               with_noise_ops, fold);
     int b = 0;
     if constexpr (kTree) {
         // exclusive prefix E_c = T_{c-1} ... T_0 of the chunk totals as an ordered pairwise tree
         // (newer factor on the left), several products per pass: ceil(log2 c) dependent levels
         // instead of c - 1 dependent products.  In place: pass j writes slot j after reading slots
         // 2j and 2j+1, which no later pass of the level reads.
-        constexpr int DD = D*D, PER = 64/DD;
-        for (int e = lane; e < c*DD; e += 64) (&tot[0][0][0])[e] = totals[e];
-        __syncthreads();
-        int n = c;
+        constexpr int PER = 64/DD;
+        int n = c;                                  // (the totals: in `tot` since the top of the block)
         while (n > 1) {
             const int pairs = n >> 1;
             for (int j0 = 0; j0 < pairs; j0 += PER) {
@@ -298,7 +460,6 @@ __device__ __forceinline__ void apply_prologue_segment(
     }
     }
     // Q[g] (into LDS) and Q[g+1] (to memory)
-    for (int e = lane; e < D*D; e += 64) M[e / D][e % D] = Qloc[static_cast<size_t>(g + 1)*D*D + e];
     if (g == 0)
         for (int e = lane; e < D*D; e += 64) Qout[e] = {(e / D == e % D) ? 1.0 : 0.0, 0.0};
     __syncthreads();
@@ -309,25 +470,20 @@ __device__ __forceinline__ void apply_prologue_segment(
         for (int x = 0; x < D; ++x) cmac(acc, M[i][x], E[b][x][j]);
         Qout[static_cast<size_t>(g + 1)*D*D + e] = acc;
     }
-    if (segtab == nullptr) return;
-    __syncthreads();
+    if (!prologue) return;
     if (g % L == 0) {
         for (int e = lane; e < D*D; e += 64) Q[e / D][e % D] = E[b][e / D][e % D];
     } else {
-        for (int e = lane; e < D*D; e += 64) M[e / D][e % D] = Qloc[static_cast<size_t>(g)*D*D + e];
-        __syncthreads();
         for (int e = lane; e < D*D; e += 64) {
             const int i = e / D, j = e % D;
             cplx acc = {0.0, 0.0};
 #pragma unroll
-            for (int x = 0; x < D; ++x) cmac(acc, M[i][x], E[b][x][j]);
+            for (int x = 0; x < D; ++x) cmac(acc, Mg[i][x], E[b][x][j]);
             Q[i][j] = acc;
         }
     }
-    for (int e = lane; e < D*D; e += 64) V[e / D][e % D] = eigvecs[static_cast<size_t>(g)*D*D + e];
     __syncthreads();
-    prologue_segment<D>(V, Q, T, BV, g, lane, eigvals, n_opers, n_coeffs, dt, t, G, A, segtab, Tc,
-                        ops, nullptr, nullptr, with_noise_ops, wfold);
+    prologue_back<D>(V, Q, T, BV, Bl, eb, g, lane, A, Tc, ops, nullptr, fold, wfold);
 }
 
 template <int D>

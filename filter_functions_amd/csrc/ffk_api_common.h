@@ -14,6 +14,7 @@
 //   ffk_api_batch.hip     many pulses of one shape in one pass of the pipeline (ffk_pipeline_batch_dev)
 //   ffk_api_batch_grad.hip  the gradient of the filter function / infidelity of many pulses in one pass
 //   ffk_api_batch_second.hip  the frequency shifts of many pulses in one pass, without F2 in memory
+//   ffk_api_periodic.hip  periodic driving: many pulses at many repeat counts in one pass
 #pragma once
 #include <cstdarg>
 #include <cstdio>
@@ -150,6 +151,14 @@ int pipeline_batch_dev_impl(int P, const double* c_opers, int n_cops, const doub
                             const int32_t* idx, int n_idx, int d_infidelity, double* eigvals, double* eigvecs,
                             double* propagators, double* control_matrix, double* filter_function, double* infid,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+// ffk_api_resident.hip, for the passes of other translation units that read resident control matrices in place
+// (ffk_api_periodic.hip): where each of n control matrices (A, N, W) lies on `device` -- in its handle (slot < 0: its
+// single result, else that member of its pass), or, no handle, NULL: a row of the host table the caller uploads,
+// counted in n_host.
+int resident_locate_control_matrices(ffk_resident* const* handles, const int32_t* slots, int n, int device, int A,
+                                     int N, int W, const char* what, std::vector<const unsigned char*>* at,
+                                     int* n_host);
 
 // Scratch from the shared arena is handed to kernels on a non-blocking stream while g_arena.mu is
 // held; the lock may only be dropped once that stream has drained -- on EVERY exit path, also the

@@ -250,6 +250,12 @@ int locate_gates(const GateTable& g, int device, std::vector<const unsigned char
 
 }  // namespace
 
+int ffk_api::resident_locate_control_matrices(ffk_resident* const* handles, const int32_t* slots, int n, int device,
+                                              int A, int N, int W, const char* what,
+                                              std::vector<const unsigned char*>* at, int* n_host) {
+    return locate_control_matrices(handles, slots, n, device, 0, A, N, W, what, at, n_host);
+}
+
 extern "C" {
 
 int ffk_resident_create(ffk_resident** out) {

@@ -621,6 +621,23 @@ __host__ __device__ inline int expm_squarings(double norm) {
     return squarings;
 }
 
+// ---- periodic_batch.hip ----------------------------------------------------------------------
+// Periodic driving of P pulses (2 <= d <= 4, N = d^2 basis elements) at K repeat counts, from Rtab: P device pointers
+// to one period's control matrices (A, N, W); V (P, d, d) unitary eigenvectors of the total propagators and phi
+// (P, d, d, 2) the differences phi_j - phi_k of their eigenphases as hi + lo, period (P) the durations, repeats (K) int32 >= 1, ops (n_ops) the selected noise operators;
+// scale from launch_spectral_weights (s_ndim 1: one row, 2: one per selected operator; real parts are read).
+// fejer: F (P, K, n_ops, W) and / or infid (P, K, n_ops) (needs scale), either may be NULL; decay: gamma
+// (P, K, n_ops, N, N), symmetric bit for bit.  One launch each, whatever P and K; no workspace.
+bool periodic_supported(int P, int K, int d, int W, int n_ops);
+hipError_t launch_periodic_fejer(const cplx* const* Rtab, int P, int d, int W, const cplx* basis, const cplx* V,
+                                 const double* phi, const double* period, const double* omega,
+                                 const int32_t* repeats, int K, const int32_t* ops, int n_ops, const cplx* scale,
+                                 int s_ndim, int d_infidelity, double* F, double* infid, hipStream_t stream);
+hipError_t launch_periodic_decay(const cplx* const* Rtab, int P, int d, int W, const cplx* basis, const cplx* V,
+                                 const double* phi, const double* period, const double* omega,
+                                 const int32_t* repeats, int K, const int32_t* ops, int n_ops, const cplx* scale,
+                                 int s_ndim, double* gamma, hipStream_t stream);
+
 // ---- processes.hip ---------------------------------------------------------------------------
 // Gamma (P, pairs, N, N) f64 of P independent pulses, N <= 16, pairs = n_idx (s_ndim 1, 2) or n_idx^2 (3), from
 // Rtab: P device pointers to control matrices (A, N, W); scale from launch_spectral_weights (rows of W);

@@ -799,6 +799,40 @@ int ffk_resident_batch_processes(ffk_resident* const* pulses, const int32_t* slo
                                  double* decay_amplitudes, double* cumulant_function, double* error_transfer_matrix,
                                  int32_t* not_finite);
 
+/* ---- periodic driving: P pulses at K repeat counts in ONE pass (ff.periodic_filter_functions,
+ *      ff.periodic_infidelities, ff.periodic_decay_amplitudes) ----
+ * Pulse p is one period: its control matrix (A, N = d^2, W) on the grid omega (W,), the eigensystem of its total
+ * propagator U = V diag(e^{i phi}) V^dag -- eigvecs (P, d, d) c128 with UNITARY V also where phases coincide,
+ * phase_differences (P, d, d, 2) f64: phi_j - phi_k as an unevaluated sum hi + lo of two doubles (lo may be 0) -- and
+ * its duration periods (P,) f64.  basis (N, d, d) c128: complete, orthonormal, Hermitian.  repeats
+ * (K,) int32 >= 1 is shared by all pulses.  In U's eigenbasis the control matrix of n periods is that of one period
+ * times sum_{g<n} e^{i g theta_jk}, theta_jk = fl(omega T) - (phi_j - phi_k): the repeat count enters as the argument
+ * of a sine, evaluated as sin(n theta/2)/sin(theta/2) on the angle reduced to [-pi, pi] (n where the sine vanishes).
+ * stage selects `out`: 1 the fidelity filter functions' diagonal (P, K, n_idx, W) f64 (no spectrum needed), 2 the
+ * infidelities (P, K, n_idx) f64 = sum_w weight(w) F(w) / d_infidelity, 3 the decay amplitudes (P, K, n_idx, N, N)
+ * f64, symmetric bit for bit.  spectrum c128 (W,) for s_ndim = 1 or (n_idx, W) for s_ndim = 2 (its real part is
+ * used; cross-spectra are not taken), idx (n_idx,) int32 the selected noise operators, W >= 2 at stage 2 and 3.
+ * A result does not depend on what else is in the pass, nor on its place in it.  One launch per stage (two with
+ * the weights) whatever P and K.  Supported: 2 <= d <= 4, 1 <= P, K <= 65535, 1 <= n_idx <= A.
+ *   ffk_periodic_dev: device pointers (control_matrices: P device pointers in device memory); launches only.
+ *     workspace: 16 * rows * W bytes (rows = 1 or n_idx) at stage 2 and 3, none at stage 1.
+ *   ffk_resident_periodic: host pointers; pulses[p] an ffk_resident* with slots[p] as for
+ *     ffk_resident_batch_processes, or NULL: the next row of control_matrices (n_host, A, N, W) c128 host.  One
+ *     staged call through the arena: the inputs up, the kernels, `out` back.  Bad arguments (a repeat count below 1
+ *     among them): FFK_EINVAL before anything touches the device.
+ *   ffk_periodic_workspace_bytes: the device bytes that call stages (0: unsupported shape). */
+size_t ffk_periodic_workspace_bytes(int P, int K, int n_host, int A, int W, int d, int n_idx, int s_ndim, int stage);
+int ffk_periodic_dev(const void* const* control_matrices, int P, int A, int W, int d, const double* omega,
+                     const double* basis, const double* eigvecs, const double* phase_differences, const double* periods,
+                     const int32_t* repeats, int K, const double* spectrum, int s_ndim, const int32_t* idx,
+                     int n_idx, int d_infidelity, int stage, double* out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int ffk_resident_periodic(ffk_resident* const* pulses, const int32_t* slots, const double* control_matrices, int P,
+                          int A, int W, int d, const double* omega, const double* basis, const double* eigvecs,
+                          const double* phase_differences, const double* periods, const int32_t* repeats, int K,
+                          const double* spectrum, int s_ndim, const int32_t* idx, int n_idx, int d_infidelity,
+                          int stage, double* out);
+
 /* ---- decay amplitudes, cumulant functions and error transfer matrices of many gate sequences from one gate set in
  *      ONE pass, under any number of spectra (ff.sequence_decay_amplitudes, ff.sequence_cumulant_functions,
  *      ff.sequence_error_transfer_matrices) ----

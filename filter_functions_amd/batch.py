@@ -213,7 +213,8 @@ def _results(pulses, omega, spectrum, n_oper_identifiers):
                   if with_integral else None)
         per_pulse = pass_bytes(len(first.dt), first.d, len(first.n_opers), len(first.basis), len(omega),
                                len(first.c_opers))
-        for chunk in split_passes(members, per_pulse):
+        # (the limits as they stand at the call: the defaults of split_passes are those of import time)
+        for chunk in split_passes(members, per_pulse, PASS_BYTES, MAX_PULSES):
             F, infid = _run_pass(pulses, chunk, first.omega, np.asarray(first.basis), parsed, idx_of[members[0]])
             if len(chunk) == len(pulses):
                 whole = F

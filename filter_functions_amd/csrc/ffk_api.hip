@@ -501,7 +501,7 @@ int control_matrix_dev_impl(const double* eigvals, const double* eigvecs, const 
     const cplx* Bsum = Ypart;
     if (expanded) {
         // R is written; F (if wanted through opt.fuse_F) is left to the caller's filter-function launch
-    } else if (compacted && control_matrix && !want_B && opt.fuse_F && ffk::expand_ff_supported(A, N)) {
+    } else if (compacted && control_matrix && !want_B && opt.fuse_F && ffk::expand_ff_supported(A, N, d)) {
         // only R and F are wanted and the basis lists are ready: chunk sum, expansion and F in one
         FFK_HIP(ffk::launch_expand_ff(Ypart, geo.chunks, slab, A, N, d, W,
                                       reinterpret_cast<cplx*>(control_matrix), opt.fuse_F, ews, s));
@@ -529,6 +529,12 @@ int control_matrix_dev_impl(const double* eigvals, const double* eigvecs, const 
     }
 
     g_stats.accumulate_flops = accumulate_flops(W, A, G, d);
+    record_accumulate_launch(W, A, G, d, geo);
+    return FFK_OK;
+}
+
+void record_accumulate_launch(int W, int A, int G, int d, const ffk::AccumGeometry& geo) {
+    const size_t slab = size_t(A)*d*d*W;
     g_stats.accumulate_bytes = double(sizeof(cplx))*(double(geo.chunks)*slab) + 8.0*W +
                                double(sizeof(cplx))*G*(double(1 + A)*d*d);
     g_stats.chunks = geo.chunks;
@@ -537,7 +543,6 @@ int control_matrix_dev_impl(const double* eigvals, const double* eigvecs, const 
     g_stats.grid_z = geo.chunks;
     g_stats.block = geo.nwaves*geo.gsplit*64;
     g_stats.lds_bytes = geo.lds_bytes;
-    return FFK_OK;
 }
 }  // namespace ffk_api
 extern "C" {

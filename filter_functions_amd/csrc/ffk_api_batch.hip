@@ -2,7 +2,7 @@
 // grid axis, every per-pulse array pulse-major.  Shared by all pulses: the frequency grid, the basis, the spectrum and
 // idx.  The single-pulse entry points and their kernels are untouched.
 //
-// Stages (fused front: use_fused_front(G, d) and expand_ff_supported(A, N)):
+// Stages (fused front: use_fused_front(G, d) and expand_ff_supported(A, N, d)):
 //   eigh_expm_controls_pulses  (G, P)     H summed from the pulse's own controls, eigensystem, segment propagators
 //   scan_local_pulses          (chunks, P) chunk-local prefix products; a chunk never straddles two pulses
 //   apply_prologue_pulses      (G + N, P) scan fix-up from the pulse's own chunk totals + prologue; basis compacted once
@@ -18,7 +18,7 @@ namespace ffk_api {
 namespace {
 
 bool batch_fused(int W, int N, int A, int G, int d) {
-    return ffk::use_fused_front(G, d) && ffk::expand_ff_supported(A, N);
+    return ffk::use_fused_front(G, d) && ffk::expand_ff_supported(A, N, d);
 }
 
 struct BatchWs {
@@ -121,6 +121,8 @@ int pipeline_batch_dev_impl(int P, const double* c_opers, int n_cops, const doub
         // dimension's own kernel reads it)
         FFK_HIP(ffk::launch_accumulate(omega, W, w.segtab, w.ops, P*G, d, A, geo, w.Ypart, s, nullptr, nullptr,
                                        w.wfold));
+        g_stats.accumulate_flops = 0.0;         // (no model of the batched launch; include/ffk.h)
+        record_accumulate_launch(W, A, P*G, d, geo);
         FFK_HIP(ffk::launch_expand_ff_pulses(w.Ypart, geo.chunks/P, size_t(A)*dd*W, A, N, d, W, P,
                                              reinterpret_cast<cplx*>(R), reinterpret_cast<cplx*>(F), w.ews, s));
     } else {

@@ -327,6 +327,8 @@ inline SpectrumShape spectrum_shape(int s_ndim, int n_idx) {
 size_t ctrl_ws_bytes(int W, int N, int A, int G, int d, int chunks);
 int max_chunks_for(int W, int A, int G, int d);
 double accumulate_flops(int W, int A, int G, int d);
+// the geometry fields and the bytes of g_stats for an accumulate launch over G segments (ffk_get_stats)
+void record_accumulate_launch(int W, int A, int G, int d, const ffk::AccumGeometry& geo);
 
 // diagonalize workspace: [status: G ints][seg_prop: G d^2][Qloc: (G+1) d^2][totals / scan scratch]
 struct DiagWs {

@@ -307,7 +307,7 @@ void expand_workspace_slices(void* ws, int N, int d, int** nnz, int** rows, cplx
 hipError_t launch_expand_chunks(const cplx* Ypart, int chunks, size_t slab, int A, int N, int d,
                                 int W, cplx* R, void* ws, hipStream_t stream);
 // ... and the fidelity filter function F (A,A,W) in the same launch (small A*N)
-bool expand_ff_supported(int A, int N);
+bool expand_ff_supported(int A, int N, int d);
 hipError_t launch_expand_ff(const cplx* Ypart, int chunks, size_t slab, int A, int N, int d, int W,
                             cplx* R, cplx* F, void* ws, hipStream_t stream);
 // ... for P pulses: block (frequency tile, pulse), pulse p sums Ypart[p chunks .. (p+1) chunks); R (P,A,N,W), F (P,A,A,W)

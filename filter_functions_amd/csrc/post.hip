@@ -951,14 +951,26 @@ __global__ __launch_bounds__(256) void expand_ff_pulses_kernel(const cplx* __res
                    R + p*A*N*W, F + p*A*A*W);
 }
 
-bool expand_ff_supported(int A, int N) {
-    // R tile [A][N][16] + summed partials [A][d^2][16], d^2 <= N for a complete basis; N bounds both
-    return static_cast<size_t>(A)*2*N*16*sizeof(cplx) <= 128*1024;
+// LDS of one expansion block, the one figure behind the predicate and both launches: the R tile [A][N][16] and the
+// summed partials [A][d^2][16], then the basis lists where they are small.  N may be smaller than d^2 (an incomplete
+// basis): the partials are the larger tile then, and N alone bounds nothing.
+static size_t expand_ff_tile_bytes(int A, int N, int d) {
+    return static_cast<size_t>(A)*(static_cast<size_t>(N) + static_cast<size_t>(d)*d)*16*sizeof(cplx);
+}
+static size_t expand_ff_lds_bytes(int A, int N, int d) {
+    return expand_ff_tile_bytes(A, N, d) + expand_ff_list_bytes(N, d*d);
+}
+
+bool expand_ff_supported(int A, int N, int d) {
+    // 128 KiB of tiles (for a complete basis, N = d^2, that is A 2 N 16 sizeof(cplx)); the lists add kExpandListCap
+    // at most, so whatever passes here fits the launches' 160 KiB
+    static_assert(128*1024 + kExpandListCap <= 160*1024, "tiles and lists must fit the LDS of a CU");
+    return expand_ff_tile_bytes(A, N, d) <= 128*1024;
 }
 
 hipError_t launch_expand_ff(const cplx* Ypart, int chunks, size_t slab, int A, int N, int d, int W,
                             cplx* R, cplx* F, void* ws, hipStream_t stream) {
-    if (!expand_ff_supported(A, N)) return hipErrorInvalidValue;
+    if (!expand_ff_supported(A, N, d)) return hipErrorInvalidValue;
     const CompactWs cw = slice_compact_ws(ws, N, d);
     const int kt = N >= 16 ? 16 : (N >= 8 ? 8 : 4);
     // block = 16 x kt x at <= 256 threads (one wave per SIMD): a 768-thread block of this kernel does
@@ -966,7 +978,7 @@ hipError_t launch_expand_ff(const cplx* Ypart, int chunks, size_t slab, int A, i
     // do not) and then waits for that whole kernel -- with the front of the next-but-one pass queued
     // behind it on the same stream
     const int at = std::max(1, std::min(A, 16/kt));
-    const size_t lds = static_cast<size_t>(A)*(N + d*d)*16*sizeof(cplx) + expand_ff_list_bytes(N, d*d);
+    const size_t lds = expand_ff_lds_bytes(A, N, d);
     if (lds > 160*1024) return hipErrorInvalidValue;
     if (lds > 48*1024) {
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(expand_ff_kernel),
@@ -981,11 +993,11 @@ hipError_t launch_expand_ff(const cplx* Ypart, int chunks, size_t slab, int A, i
 
 hipError_t launch_expand_ff_pulses(const cplx* Ypart, int chunks, size_t slab, int A, int N, int d, int W,
                                    int P, cplx* R, cplx* F, void* ws, hipStream_t stream) {
-    if (!expand_ff_supported(A, N) || P < 1 || P > 65535) return hipErrorInvalidValue;
+    if (!expand_ff_supported(A, N, d) || P < 1 || P > 65535) return hipErrorInvalidValue;
     const CompactWs cw = slice_compact_ws(ws, N, d);
     const int kt = N >= 16 ? 16 : (N >= 8 ? 8 : 4);
     const int at = std::max(1, std::min(A, 16/kt));
-    const size_t lds = static_cast<size_t>(A)*(N + d*d)*16*sizeof(cplx) + expand_ff_list_bytes(N, d*d);
+    const size_t lds = expand_ff_lds_bytes(A, N, d);
     if (lds > 160*1024) return hipErrorInvalidValue;
     if (lds > 48*1024) {
         hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(expand_ff_pulses_kernel),

@@ -1009,7 +1009,10 @@ int ffk_set_segment_chunks(int chunks);
  * kernel (d >= 12 use it by default), 4 = use the matrix-core kernel wherever it exists (d = 8 too). */
 int ffk_set_accumulate_variant(int variant);
 /* Per-call statistics of the last ffk_control_matrix*_dev launch on this thread:
- * algorithmic FP64 flops of the accumulate kernel, its grid/block geometry, chunks used.   */
+ * algorithmic FP64 flops of the accumulate kernel, its grid/block geometry, chunks used.
+ * A batched pass (ffk_pipeline_batch_dev) on its fused route records its one accumulate launch over
+ * the P G segments: chunks = grid_z = P x (chunks per pulse), accumulate_flops = 0 (not modelled);
+ * where it runs P single passes it leaves the last of them.                                  */
 typedef struct ffk_stats {
     double accumulate_flops;   /* FMA-counted real flops ffk::ctrl_accumulate executes      */
     double accumulate_bytes;   /* HBM bytes it must move (inputs + partial sums)            */

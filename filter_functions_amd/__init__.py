@@ -13,7 +13,7 @@ The arithmetic runs in hand-written HIP kernels for gfx950 behind a C ABI
 side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
-from . import (analytic, basis, batch, batch_gradient, batch_second_order, correlations, expm_batch, gradient, numeric, periodic, processes, pulse_sequence, sequences,
+from . import (analytic, basis, batch, batch_gradient, batch_second_order, correlations, expm_batch, gradient, numeric, periodic, periodic_second_order, processes, pulse_sequence, sequences,
                sequence_prefix_second_order, sequence_prefixes, sequence_processes, sequence_second_order, superoperator,
                util)
 from .basis import Basis
@@ -25,6 +25,8 @@ from .expm_batch import exponentiate_cumulant_functions
 from .gradient import infidelity_derivative
 from .numeric import error_transfer_matrix, infidelity
 from .periodic import periodic_decay_amplitudes, periodic_filter_functions, periodic_infidelities
+from .periodic_second_order import (periodic_cumulant_functions, periodic_error_transfer_matrices,
+                                    periodic_frequency_shifts)
 from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
 from .sequences import concatenate_sequences
 from .sequence_correlations import sequence_correlation_infidelities
@@ -49,7 +51,8 @@ __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradie
            'error_transfer_matrices', 'error_transfer_matrix', 'expm_batch', 'exponentiate_cumulant_functions', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
            'filter_function_derivatives', 'frequency_shifts', 'infidelity_derivative', 'infidelity_derivatives',
            'liouville_representation', 'numeric', 'periodic', 'periodic_decay_amplitudes',
-           'periodic_filter_functions', 'periodic_infidelities', 'processes',
+           'periodic_cumulant_functions', 'periodic_error_transfer_matrices', 'periodic_filter_functions',
+           'periodic_frequency_shifts', 'periodic_infidelities', 'periodic_second_order', 'processes',
            'pulse_sequence', 'remap', 'sequence_correlation_infidelities', 'sequence_correlations',
            'sequence_cumulant_functions', 'sequence_decay_amplitudes',
            'sequence_error_transfer_matrices', 'sequence_frequency_shifts', 'sequence_infidelities',

@@ -290,6 +290,13 @@ SIGNATURES = {
     'ffk_resident_periodic': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                       c_int, c_int, c_void_p]),
+    'ffk_periodic_shifts_workspace_bytes': (c_size_t, [c_int]*9),
+    'ffk_periodic_shifts_dev': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'ffk_resident_periodic_shifts': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                             c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'ffk_sequence_processes_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                           c_int, c_int, c_int, c_int]),
     'ffk_sequence_processes': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,

@@ -637,6 +637,19 @@ hipError_t launch_periodic_decay(const cplx* const* Rtab, int P, int d, int W, c
                                  const double* phi, const double* period, const double* omega,
                                  const int32_t* repeats, int K, const int32_t* ops, int n_ops, const cplx* scale,
                                  int s_ndim, double* gamma, hipStream_t stream);
+// Second order by period doubling: steps (S, 4) int32 = (m, m', slot of Delta_m, slot of Delta_m') per step, the
+// result of step s in slot s + 1, slot 0 = delta1 (P, n_ops, N, N); count_slots (K) the slot each count reads.
+// gram: tiles (P, n_ops, S, N, N) = X(m, m') of every step (S >= 1); combine: walks the steps on table
+// (P, n_ops, S + 1, N, N) and writes out (P, K, n_ops, N, N).  One launch each whatever P, K and S.
+bool periodic_shifts_supported(int P, int K, int S, int d, int W, int n_ops);
+hipError_t launch_periodic_shift_gram(const cplx* const* Rtab, int P, int d, int W, const cplx* basis, const cplx* V,
+                                      const double* phi, const double* period, const double* omega,
+                                      const int32_t* steps, int S, const int32_t* ops, int n_ops, const cplx* scale,
+                                      int s_ndim, double* tiles, hipStream_t stream);
+hipError_t launch_periodic_shift_combine(int P, int d, const cplx* basis, const cplx* V, const double* phi,
+                                         const int32_t* steps, int S, const int32_t* count_slots, int K, int n_ops,
+                                         const double* delta1, const double* tiles, double* table, double* out,
+                                         hipStream_t stream);
 
 // ---- processes.hip ---------------------------------------------------------------------------
 // Gamma (P, pairs, N, N) f64 of P independent pulses, N <= 16, pairs = n_idx (s_ndim 1, 2) or n_idx^2 (3), from

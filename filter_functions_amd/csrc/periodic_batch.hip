@@ -375,4 +375,268 @@ hipError_t launch_periodic_decay(const cplx* const* Rtab, int P, int d, int W, c
     return hipGetLastError();
 }
 
+// ---- second order: frequency shifts by period doubling -----------------------------------
+// The concatenation rule of the second-order filter function, integrated, for an atom of m periods followed by one
+// of m' periods of the same pulse:
+//     Delta_{m+m'} = Delta_m + Q_m^T Delta_{m'} Q_m + X(m, m'),
+//     X(m, m')[k,l] = sum_w c_w Re( conj( e^{i w m T} (R_{m'} Q_m)[k,w] ) R_m[l,w] ),
+// Q_m the Liouville matrix of U^m.  In U's eigenbasis both operands are element-wise in what periodic_decay_kernel
+// forms: R_m <-> B_e = X'_e s_e(m), and e^{i w m T} R_{m'} Q_m <-> A_e = X'_e s_e(m') e^{i m theta_e} (the terms
+// g = m .. m + m' - 1 of the sum), so that
+//     M[e,f] = sum_w c_w conj(A_e) B_f   (d^2 x d^2 complex, not Hermitian),
+//     X[k,l] = Re sum_ef conj(E[e,k]) M[e,f] E[f,l],
+//     Q_m[i,j] = Re sum_ab e^{-i m (phi_a - phi_b)} C'_i[a,b] C'_j[b,a].
+// A host-made plan of steps (m, m', slot of Delta_m, slot of Delta_m') reaches every count in O(log n) steps; the
+// result of step s lies in slot s + 1, slot 0 is Delta_1.
+namespace {
+
+// Block (selected operator i, step s, pulse p), four wavefronts, as periodic_decay_kernel: steps of 64 frequencies,
+// wavefront g fills the two operands of the entries e = g, g + 4, ... into LDS; then M of the step --
+//   d = 4: four real chains on v_mfma_f64_16x16x4_f64, Re = Ar^T c Br + Ai^T c Bi, Im = Ar^T c Bi - Ai^T c Br, the four
+//          wavefronts' tiles added in index order after the last step (their LDS is that of the operands, reused);
+//   d = 2, 3: thread (e, f), vector FMAs over the 64 frequencies in order.
+// Then T = M E and X[k,l] = Re sum_e conj(E[e,k]) T[e,l] for all (k, l) into tiles (P, n_ops, S, N, N).
+template <int D>
+__global__ __launch_bounds__(kThreads) void periodic_shift_gram_kernel(
+    const cplx* const* __restrict__ Rtab, const cplx* __restrict__ basis, const cplx* __restrict__ Vall,
+    const double* __restrict__ phiall, const double* __restrict__ period, const double* __restrict__ omega, int W,
+    const int32_t* __restrict__ steps, int S, const int32_t* __restrict__ ops, int n_ops,
+    const cplx* __restrict__ scale, int s_ndim, double* __restrict__ tiles) {
+    constexpr int DD = D*D, PER = (DD + 3)/4, PLANE = DD*kPad;
+    constexpr int PART = D == 4 ? 4*4*16*17 : 0;
+    constexpr int BUF = PART > 4*PLANE ? PART : 4*PLANE;
+    __shared__ cplx Cp[DD*DD];
+    __shared__ double dphi[2*DD];
+    __shared__ double buf[BUF], cw[kChunk];
+    __shared__ cplx M[DD*DD], Tm[DD*DD];
+    double* const Ar = buf;
+    double* const Ai = buf + PLANE;
+    double* const Br = buf + 2*PLANE;
+    double* const Bi = buf + 3*PLANE;
+    const int i = blockIdx.x, s = blockIdx.y, p = blockIdx.z;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    rotate_basis<D, kThreads>(basis, Vall + static_cast<size_t>(p)*DD, phiall + static_cast<size_t>(p)*2*DD, Cp, dphi);
+    __syncthreads();
+    const double T = period[p];
+    const double m = static_cast<double>(steps[4*s]), mp = static_cast<double>(steps[4*s + 1]);
+    const cplx* R = Rtab[p] + static_cast<size_t>(ops[i])*DD*W;
+    const cplx* sc = scale + static_cast<size_t>(s_ndim == 1 ? 0 : i)*W;
+    const int ge = threadIdx.x / DD, gf = threadIdx.x % DD;
+    cplx acc = {0.0, 0.0};
+    f64x4 acc_rr = {0.0, 0.0, 0.0, 0.0}, acc_ii = {0.0, 0.0, 0.0, 0.0}, acc_ri = {0.0, 0.0, 0.0, 0.0},
+          acc_ir = {0.0, 0.0, 0.0, 0.0};
+    for (int w0 = 0; w0 < W; w0 += kChunk) {
+        const int w = w0 + lane;
+        const bool valid = w < W;
+        const int wc = valid ? w : W - 1;
+        cplx X[PER];
+#pragma unroll
+        for (int u = 0; u < PER; ++u) X[u] = {0.0, 0.0};
+        for (int l = 0; l < DD; ++l) {
+            const cplx r = R[static_cast<size_t>(l)*W + wc];
+#pragma unroll
+            for (int u = 0; u < PER; ++u) {
+                const int e = min(wave + 4*u, DD - 1);
+                cmac(X[u], r, Cp[l*DD + e]);
+            }
+        }
+        const HalfAngle x = reduce_two_pi(omega[wc]*T);
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int e = wave + 4*u;
+            if (e < DD) {
+                const HalfAngle h = half_angle(x, dphi[2*e], dphi[2*e + 1]);
+                const cplx sm = dirichlet_factor(h, m);
+                const cplx smp = mp == m ? sm : dirichlet_factor(h, mp);
+                // e^{i m theta} = e^{i (2 m) h}: the multiplier is exact as a double
+                cplx ph;
+                sincos_multiple<true>(2.0*m, h, &ph.im, &ph.re);
+                const cplx a = cmul(cmul(X[u], smp), ph);
+                const cplx b = cmul(X[u], sm);
+                Ar[e*kPad + lane] = valid ? a.re : 0.0;
+                Ai[e*kPad + lane] = valid ? a.im : 0.0;
+                Br[e*kPad + lane] = valid ? b.re : 0.0;
+                Bi[e*kPad + lane] = valid ? b.im : 0.0;
+            }
+        }
+        if (wave == 0) cw[lane] = valid ? sc[wc].re : 0.0;
+        __syncthreads();
+        if constexpr (D == 4) {
+            const int c = lane & 15, r4 = lane >> 4;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int wl = 16*wave + 4*q + r4;
+                const double cc = cw[wl];
+                const double ar = Ar[c*kPad + wl], ai = Ai[c*kPad + wl];
+                const double br = cc*Br[c*kPad + wl], bi = cc*Bi[c*kPad + wl];
+                acc_rr = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, acc_rr, 0, 0, 0);
+                acc_ii = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bi, acc_ii, 0, 0, 0);
+                acc_ri = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi, acc_ri, 0, 0, 0);
+                acc_ir = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, acc_ir, 0, 0, 0);
+            }
+        } else {
+            if (threadIdx.x < DD*DD) {
+                for (int wl = 0; wl < kChunk; ++wl) {
+                    const double cc = cw[wl];
+                    const cplx a = {Ar[ge*kPad + wl], Ai[ge*kPad + wl]};
+                    const cplx b = {cc*Br[gf*kPad + wl], cc*Bi[gf*kPad + wl]};
+                    cmac_conj(acc, a, b);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if constexpr (D == 4) {
+        // (the operands' LDS is free after the last step's barrier)
+        double* const part = buf;
+        const int c = lane & 15, r4 = lane >> 4;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            part[((wave*4 + 0)*16 + r4 + 4*r)*17 + c] = acc_rr[r];
+            part[((wave*4 + 1)*16 + r4 + 4*r)*17 + c] = acc_ii[r];
+            part[((wave*4 + 2)*16 + r4 + 4*r)*17 + c] = acc_ri[r];
+            part[((wave*4 + 3)*16 + r4 + 4*r)*17 + c] = acc_ir[r];
+        }
+        __syncthreads();
+        // thread (e, f): the tiles of the four wavefronts in index order
+        double re = 0.0, im = 0.0;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            re += part[((g*4 + 0)*16 + ge)*17 + gf] + part[((g*4 + 1)*16 + ge)*17 + gf];
+            im += part[((g*4 + 2)*16 + ge)*17 + gf] - part[((g*4 + 3)*16 + ge)*17 + gf];
+        }
+        acc = {re, im};
+    }
+    if (threadIdx.x < DD*DD) M[ge*DD + gf] = acc;
+    __syncthreads();
+    // E[f][l] = C'_l[m, j] with f = (j, m):  Cp[l DD + m D + j]
+    if (threadIdx.x < DD*DD) {
+        const int e = ge, l = gf;
+        cplx t = {0.0, 0.0};
+#pragma unroll
+        for (int f = 0; f < DD; ++f) cmac(t, M[e*DD + f], Cp[l*DD + (f % D)*D + f / D]);
+        Tm[e*DD + l] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < DD*DD) {
+        const int k = ge, l = gf;
+        double re = 0.0;
+#pragma unroll
+        for (int e = 0; e < DD; ++e) {
+            const cplx a = Cp[k*DD + (e % D)*D + e / D];
+            const cplx t = Tm[e*DD + l];
+            re = fma(a.re, t.re, re);
+            re = fma(a.im, t.im, re);
+        }
+        tiles[((static_cast<size_t>(p)*n_ops + i)*S + s)*DD*DD + k*DD + l] = re;
+    }
+}
+
+// Block (selected operator i, pulse p) walks the plan serially.  Per step: the phases e^{-i m (phi_a - phi_b)} from
+// the hi + lo differences (reduced as every other angle, the multiplier 2 m on the half angle), Q_m in LDS, then
+// table[s + 1] = table[slot_m] + Q_m^T table[slot_m'] Q_m + X[s], in that order.  The table (P, n_ops, S + 1, N, N)
+// lies in device memory: a block reads back only what it wrote itself, behind a barrier.  Last, the K rows of `out`
+// (P, K, n_ops, N, N) are copied from the slots of the counts: with no step at all, Delta_1 bit for bit.
+template <int D>
+__global__ __launch_bounds__(kThreads) void periodic_shift_combine_kernel(
+    const cplx* __restrict__ basis, const cplx* __restrict__ Vall, const double* __restrict__ phiall,
+    const int32_t* __restrict__ steps, int S, const int32_t* __restrict__ count_slots, int K, int n_ops,
+    const double* __restrict__ delta1, const double* __restrict__ tiles, double* table, double* __restrict__ out) {
+    constexpr int DD = D*D, NN = DD*DD;
+    __shared__ cplx Cp[NN];
+    __shared__ double dphi[2*DD];
+    __shared__ cplx ph[DD];
+    __shared__ double Q[NN], Tm[NN];
+    const int i = blockIdx.x, p = blockIdx.y, t = threadIdx.x;
+    const int k = t / DD, l = t % DD;
+    const size_t member = static_cast<size_t>(p)*n_ops + i;
+    rotate_basis<D, kThreads>(basis, Vall + static_cast<size_t>(p)*DD, phiall + static_cast<size_t>(p)*2*DD, Cp, dphi);
+    double* tab = table + member*(static_cast<size_t>(S) + 1)*NN;
+    const double* X = tiles + member*static_cast<size_t>(S)*NN;
+    if (t < NN) tab[t] = delta1[member*NN + t];
+    __syncthreads();
+#pragma unroll 1
+    for (int s = 0; s < S; ++s) {
+        const double m = static_cast<double>(steps[4*s]);
+        const size_t at_m = static_cast<size_t>(steps[4*s + 2])*NN, at_mp = static_cast<size_t>(steps[4*s + 3])*NN;
+        if (t < DD) {
+            const HalfAngle h = half_angle(HalfAngle{0.0, 0.0}, dphi[2*t], dphi[2*t + 1]);
+            cplx e;
+            sincos_multiple<true>(2.0*m, h, &e.im, &e.re);
+            ph[t] = e;
+        }
+        __syncthreads();
+        if (t < NN) {
+            double q = 0.0;
+#pragma unroll
+            for (int ab = 0; ab < DD; ++ab) {
+                const cplx c = cmul(Cp[k*DD + ab], Cp[l*DD + (ab % D)*D + ab / D]);
+                q = fma(ph[ab].re, c.re, q);
+                q = fma(-ph[ab].im, c.im, q);
+            }
+            Q[t] = q;
+        }
+        __syncthreads();
+        if (t < NN) {
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < DD; ++q) v = fma(tab[at_mp + k*DD + q], Q[q*DD + l], v);
+            Tm[t] = v;
+        }
+        __syncthreads();
+        if (t < NN) {
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < DD; ++q) v = fma(Q[q*DD + k], Tm[q*DD + l], v);
+            tab[(static_cast<size_t>(s) + 1)*NN + t] = (tab[at_m + t] + v) + X[static_cast<size_t>(s)*NN + t];
+        }
+        __syncthreads();
+    }
+    for (int item = t; item < K*NN; item += kThreads) {
+        const int q = item / NN, x = item % NN;
+        out[((static_cast<size_t>(p)*K + q)*n_ops + i)*NN + x] = tab[static_cast<size_t>(count_slots[q])*NN + x];
+    }
+}
+
+}  // namespace
+
+bool periodic_shifts_supported(int P, int K, int S, int d, int W, int n_ops) {
+    return periodic_supported(P, K, d, W, n_ops) && S >= 0 && S <= 65535 && W >= 2;
+}
+
+hipError_t launch_periodic_shift_gram(const cplx* const* Rtab, int P, int d, int W, const cplx* basis, const cplx* V,
+                                      const double* phi, const double* period, const double* omega,
+                                      const int32_t* steps, int S, const int32_t* ops, int n_ops, const cplx* scale,
+                                      int s_ndim, double* tiles, hipStream_t stream) {
+    if (!periodic_shifts_supported(P, 1, S, d, W, n_ops) || S < 1 || !steps || !scale || !tiles)
+        return hipErrorInvalidValue;
+    const dim3 grid(n_ops, S, P);
+#define FFK_LAUNCH(D)                                                                                                \
+    periodic_shift_gram_kernel<D><<<grid, kThreads, 0, stream>>>(Rtab, basis, V, phi, period, omega, W, steps, S,    \
+                                                                 ops, n_ops, scale, s_ndim, tiles)
+    if (d == 2) FFK_LAUNCH(2);
+    else if (d == 3) FFK_LAUNCH(3);
+    else FFK_LAUNCH(4);
+#undef FFK_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_periodic_shift_combine(int P, int d, const cplx* basis, const cplx* V, const double* phi,
+                                         const int32_t* steps, int S, const int32_t* count_slots, int K, int n_ops,
+                                         const double* delta1, const double* tiles, double* table, double* out,
+                                         hipStream_t stream) {
+    if (!periodic_shifts_supported(P, K, S, d, 2, n_ops) || !count_slots || !delta1 || !table || !out ||
+        (S > 0 && (!steps || !tiles)))
+        return hipErrorInvalidValue;
+    const dim3 grid(n_ops, P);
+#define FFK_LAUNCH(D)                                                                                                \
+    periodic_shift_combine_kernel<D><<<grid, kThreads, 0, stream>>>(basis, V, phi, steps, S, count_slots, K, n_ops,  \
+                                                                    delta1, tiles, table, out)
+    if (d == 2) FFK_LAUNCH(2);
+    else if (d == 3) FFK_LAUNCH(3);
+    else FFK_LAUNCH(4);
+#undef FFK_LAUNCH
+    return hipGetLastError();
+}
+
 }  // namespace ffk

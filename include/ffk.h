@@ -833,6 +833,40 @@ int ffk_resident_periodic(ffk_resident* const* pulses, const int32_t* slots, con
                           const double* spectrum, int s_ndim, const int32_t* idx, int n_idx, int d_infidelity,
                           int stage, double* out);
 
+/* ---- periodic driving, second order: the frequency shifts of P pulses at K repeat counts in ONE pass
+ *      (ff.periodic_frequency_shifts) ----
+ * Pulses, eigensystems, periods, basis, omega, spectrum, idx, handles and slots as for ffk_resident_periodic (W >= 2,
+ * s_ndim 1 or 2).  The counts are reached by period doubling: with Q_m the Liouville matrix of U^m and R_n the
+ * control matrix of n periods,
+ *     Delta_{m+m'} = Delta_m + Q_m^T Delta_{m'} Q_m + X(m, m'),
+ *     X(m, m')[k,l] = sum_w weight(w) Re( conj( e^{i w m T} (R_{m'} Q_m)[k,w] ) R_m[l,w] ),
+ * both operands element-wise in U's eigenbasis (sines of m theta/2 and m' theta/2 over sin(theta/2), and the phase
+ * e^{i m theta}).  steps (S, 4) int32 is the plan: per step (m, m', slot of Delta_m, slot of Delta_m'); the result of
+ * step s lies in slot s + 1 and slot 0 is delta1 (P, n_idx, N, N) f64, the pulses' own frequency shifts; a step reads
+ * slots <= s only.  count_slots (K,) int32 names the slot of each row of out (P, K, n_idx, N, N) f64.  With S = 0
+ * (steps may be NULL) every row is delta1 bit for bit.  A result depends on its own steps alone, not on what else is
+ * in the pass.  At most three launches whatever P, K and S: the weights, X of every step (grid: operator, step,
+ * pulse; d = 4 on the FP64 matrix cores), the serial walk (grid: operator, pulse).  Supported: 2 <= d <= 4,
+ * 1 <= P, K <= 65535, 0 <= S <= 65535, 1 <= n_idx <= A.
+ *   ffk_periodic_shifts_dev: device pointers; launches only.  workspace: align256(16 rows W) + align256(t S) +
+ *     align256(t (S + 1)) bytes with rows = 1 or n_idx and t = 8 P n_idx N^2.
+ *   ffk_resident_periodic_shifts: host pointers, one staged call.  Bad arguments (a step that reads a slot not yet
+ *     written among them): FFK_EINVAL before anything touches the device.
+ *   ffk_periodic_shifts_workspace_bytes: the device bytes that call stages (0: unsupported shape). */
+size_t ffk_periodic_shifts_workspace_bytes(int P, int K, int S, int n_host, int A, int W, int d, int n_idx,
+                                           int s_ndim);
+int ffk_periodic_shifts_dev(const void* const* control_matrices, int P, int A, int W, int d, const double* omega,
+                            const double* basis, const double* eigvecs, const double* phase_differences,
+                            const double* periods, const int32_t* steps, int S, const int32_t* count_slots, int K,
+                            const double* spectrum, int s_ndim, const int32_t* idx, int n_idx, const double* delta1,
+                            double* out, void* workspace, size_t workspace_bytes, void* stream);
+int ffk_resident_periodic_shifts(ffk_resident* const* pulses, const int32_t* slots, const double* control_matrices,
+                                 int P, int A, int W, int d, const double* omega, const double* basis,
+                                 const double* eigvecs, const double* phase_differences, const double* periods,
+                                 const int32_t* steps, int S, const int32_t* count_slots, int K,
+                                 const double* spectrum, int s_ndim, const int32_t* idx, int n_idx,
+                                 const double* delta1, double* out);
+
 /* ---- decay amplitudes, cumulant functions and error transfer matrices of many gate sequences from one gate set in
  *      ONE pass, under any number of spectra (ff.sequence_decay_amplitudes, ff.sequence_cumulant_functions,
  *      ff.sequence_error_transfer_matrices) ----

@@ -3,75 +3,38 @@
 // (ff.sequence_prefix_infidelities, ff.sequence_prefix_decay_amplitudes; ffk_sequence_prefix_processes).
 //
 // The concatenation rule is a sum over the positions, R = sum_g phi_{g-1} R_{k_g} Lam_g, so the control matrix of the
-// prefix of m gates is the partial sum Cum_m.  The forward walk of sequence_second_order.hip carries exactly that:
-//     X_g       = R_{k_g} Lam_g
-//     C_g       = conj(p_{k_g}) (C_{g-1} + X_g)       (= conj(phi_g) Cum_g)
-//     Lam_{g+1} = L_{k_g} Lam_g
-// and with a closing gate c_g behind the prefix the control matrix is Cum_g + phi_g R_{c_g} Lam_{g+1}, i.e.
+// prefix of m gates is the partial sum Cum_m, which the forward walk carries as C_m (sequence_walk.h: recurrences,
+// operand maps, determinism).  With a closing gate c_g behind the prefix the control matrix is
+// Cum_g + phi_g R_{c_g} Lam_{g+1}, i.e.
 //     E_g       = C_g + R_{c_g} Lam_{g+1}             (C_g itself is not changed)
 // up to the common phase phi_g, which cancels in
 //     Gamma_g[k, l] = sum_w c_w S(w) (Re E_g[k, w] Re E_g[l, w] + Im E_g[k, w] Im E_g[l, w]).
-// A prefix quantity is therefore one epilogue per position.  Position g sees nothing behind it: the curve of s[:m] is
-// the first m rows of the curve of s, bit for bit.
-//
-// A block forms the partial sums of its frequencies for every position and seqpre_reduce_kernel adds the blocks in
-// index order.  No atomics, no waits between wavefronts or blocks, a block width that depends on d and A alone, fresh
-// accumulators for every (position, operator, spectrum), at most kSpectra spectra per walk (grid z carries the
-// further ones): a position's result is the same bits whatever else is in the pass.
+// A prefix quantity is therefore one epilogue per position, from the state.  Position g sees nothing behind it: the
+// curve of s[:m] is the first m rows of the curve of s, bit for bit.  Fresh accumulators for every (position,
+// operator, spectrum), at most kSpectra spectra per walk; closing gates are a runtime pointer.
 //
 //   mode 0, 1   partial[block][position][spectrum][i][N]      sum_w c_w S(w) |E[k, w]|^2   (the diagonal of Gamma)
 //   mode 2      partial[block][position][spectrum][i][N][N]   Gamma; only k <= l is read back
 //
-//   seqpre_walk2_kernel   d = 2: lane = frequency; Lam and C per lane.  The lane-local products of a position (ten
-//                         k <= l, or four squares) are summed over the wavefront by a butterfly that halves the values
-//                         a lane carries at every step (wave_sums): about one shuffle per value, a fixed order
-//   seqpre_walk4_kernel   d = 4: v_mfma_f64_16x16x4_f64, the operand maps of seq2o_walk4_kernel.  E is C + Y with the
-//                         eight matrix instructions of Y accumulating onto C's registers; mode 2 is the Gram matrix of
-//                         E over the block's frequencies (real and imaginary chains, added at the end), modes 0 and 1
-//                         the lane's own 4 TILES frequencies in a fixed order, then the four row groups by two shuffles
+//   seqpre_walk2_kernel   d = 2: the lane-local products of a position (ten k <= l, or four squares) are summed over
+//                         the wavefront by a butterfly that halves the values a lane carries at every step
+//                         (wave_sums): about one shuffle per value, a fixed order
+//   seqpre_walk4_kernel   d = 4: E is C + Y with the eight matrix instructions of Y accumulating onto C's registers;
+//                         mode 2 is the Gram matrix of E over the block's frequencies (real and imaginary chains, added
+//                         at the end), modes 0 and 1 the lane's own 4 TILES frequencies in a fixed order, then the four
+//                         row groups by two shuffles
 //   seqpre_reduce_kernel  the frequency blocks in index order; mode 2 reads (min(k, l), max(k, l)): symmetric bit for
 //                         bit; mode 0 adds the N diagonal sums in index order and divides by d
-#include <algorithm>
-
-#include "ffk_internal.h"
+#include "sequence_walk.h"
 
 namespace ffk {
 namespace {
 
-using f64x4 = __attribute__((ext_vector_type(4))) double;
+using namespace seqwalk;
 
 constexpr int kSpectra = 2;              // spectra of one walk; grid z carries the others
-constexpr int kWaves = 4;                // one wavefront per SIMD
-
-// the row of the weights of selected operator i under spectrum sp: (n_spectra, W) or (n_spectra, n_idx, W)
-__device__ __forceinline__ const cplx* weight_row(const cplx* scale, int s_ndim, int n_idx, int sp, int i, int W) {
-    return scale + static_cast<size_t>(s_ndim == 1 ? sp : sp*n_idx + i)*W;
-}
-
-// The sums over the wavefront of VP values per lane (VP a power of two, at most 64).  At every step a lane keeps one
-// half of its values and hands the other half to its partner, so the values a lane carries halve; once one is left
-// the remaining steps are a plain butterfly.  Returns the sum of value number lane >> (6 - log2 VP), the same in the
-// 64/VP lanes that share it.  The order of the additions depends on the lane numbers alone.
-template <int VP>
-__device__ __forceinline__ double wave_sums(double (&v)[VP], int lane) {
-    int m = 32;
-#pragma unroll
-    for (int H = VP/2; H >= 1; H >>= 1, m >>= 1) {
-        const bool hi = (lane & m) != 0;
-#pragma unroll
-        for (int j = 0; j < H; ++j) {
-            const double send = hi ? v[j] : v[j + H], keep = hi ? v[j + H] : v[j];
-            v[j] = keep + __shfl_xor(send, m);
-        }
-    }
-#pragma unroll
-    for (; m >= 1; m >>= 1) v[0] += __shfl_xor(v[0], m);
-    return v[0];
-}
 
 // ---- d = 2 -------------------------------------------------------------------------------------------------------
-constexpr int kN2 = 4;
-
 template <int A, bool STAGED>
 __global__ __launch_bounds__(64*kWaves) void seqpre_walk2_kernel(
     const cplx* __restrict__ phases, const cplx* const* __restrict__ Rtab, const double* __restrict__ Lpulse,
@@ -92,26 +55,12 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk2_kernel(
     cplx* Rs = reinterpret_cast<cplx*>(lds_raw);                      // [T][ROWS][64]
     cplx* Ps = Rs + static_cast<size_t>(T)*ROWS*64;                   // [T][64]
     if (STAGED) {
-        for (int e = wave; e < T*ROWS; e += n_waves) {
-            const int k = e / ROWS, r = e % ROWS;
-            Rs[static_cast<size_t>(e)*64 + lane] = Rtab[k][static_cast<size_t>(r)*W + wc];
-        }
-        for (int k = wave; k < T; k += n_waves) Ps[k*64 + lane] = phases[static_cast<size_t>(k)*W + wc];
+        stage_tables2<ROWS>(Rs, Ps, phases, Rtab, T, W, wc, lane, wave, n_waves);
         __syncthreads();
     }
-    // which selected operator an operator is (-1: none), and its weights at this lane's frequency (0 beyond W)
     int sel[A];
     double wt[A][kSpectra];
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        sel[a] = -1;
-        for (int i = n_idx - 1; i >= 0; --i)
-            if (idx[i] == a) sel[a] = i;
-#pragma unroll
-        for (int s = 0; s < kSpectra; ++s)
-            wt[a][s] = (sel[a] >= 0 && sp0 + s < n_spectra && w < W)
-                           ? weight_row(scale, s_ndim, n_idx, sp0 + s, sel[a], W)[wc].re : 0.0;
-    }
+    select_weights2(scale, s_ndim, n_spectra, idx, n_idx, sp0, w, wc, W, sel, wt);
     // where this lane's value of a reduced set goes: value e = lane >> 2 of the ten products k <= l (mode 2), lane >> 4
     // of the four squares
     const int e10 = lane >> 2;
@@ -120,9 +69,7 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk2_kernel(
     const bool stores2 = (lane & 3) == 0 && e10 < 10, stores1 = (lane & 15) == 0;
     const size_t tile = mode == 2 ? LN : N;
     const size_t per_position = static_cast<size_t>(n_spectra)*n_idx*tile;
-    // (the small matrices are the same for every lane; read through a vector register they stay out of the scalar
-    // registers, which the pointers and counters of the walk fill)
-    int vzero;
+    int vzero;                               // (the small matrices and, read from L2, the gates' rows: sequence_walk.h)
     asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
     const int Q = n_groups*n_waves;
     for (int j = wave*n_groups + blockIdx.y; j < P; j += Q) {
@@ -136,55 +83,22 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk2_kernel(
         for (int e = 0; e < LN; ++e) Lam[e] = e % (N + 1) == 0 ? 1.0 : 0.0;
         for (int c0 = g_begin; c0 < g_end; c0 += 64) {
             const int c1 = min(g_end, c0 + 64);
-            const int my_index = c0 + lane < c1 ? index[c0 + lane] : 0;
-            const int my_closing = (closing != nullptr && c0 + lane < c1) ? closing[c0 + lane] : 0;
+            const int my_index = chunk_gates(index, true, c0, c1, lane);
+            const int my_closing = chunk_gates(closing, closing != nullptr, c0, c1, lane);
             for (int g = c0; g < c1; ++g) {
-                const int k = __builtin_amdgcn_readlane(my_index, g - c0);
-                const int kc = __builtin_amdgcn_readlane(my_closing, g - c0);
-                // (read from L2, the gates' rows are addressed through vector registers as well)
-                const int kv = STAGED ? k : k + vzero, kcv = STAGED ? kc : kc + vzero;
-                const cplx* Rg = STAGED ? Rs + static_cast<size_t>(k)*ROWS*64 + lane : Rtab[kv] + wc;
-                const cplx* Rc = STAGED ? Rs + static_cast<size_t>(kc)*ROWS*64 + lane : Rtab[kcv] + wc;
-                const size_t rstride = STAGED ? 64 : static_cast<size_t>(W + vzero);
-                const cplx ph = STAGED ? Ps[k*64 + lane] : phases[static_cast<size_t>(kv)*W + wc];
-                // C <- conj(p) (C + R_k Lam)
+                const int k = gate_at(my_index, g - c0), kc = gate_at(my_closing, g - c0);
+                const cplx* Rg = gate_rows2<ROWS, STAGED>(Rs, Rtab, k, vzero, lane, wc);
+                const cplx* Rc = gate_rows2<ROWS, STAGED>(Rs, Rtab, kc, vzero, lane, wc);
+                const size_t rstride = row_stride2<STAGED>(W, vzero);
+                const cplx ph = gate_phase2<STAGED>(Ps, phases, k, vzero, W, lane, wc);
 #pragma unroll
                 for (int a = 0; a < A; ++a) {
                     if (sel[a] < 0) continue;
                     cplx X[N];
-#pragma unroll
-                    for (int jj = 0; jj < N; ++jj) X[jj] = {0.0, 0.0};
-#pragma unroll
-                    for (int kk = 0; kk < N; ++kk) {
-                        const cplx v = Rg[(a*N + kk)*rstride];
-#pragma unroll
-                        for (int jj = 0; jj < N; ++jj) {
-                            X[jj].re = fma(v.re, Lam[kk*N + jj], X[jj].re);
-                            X[jj].im = fma(v.im, Lam[kk*N + jj], X[jj].im);
-                        }
-                    }
-#pragma unroll
-                    for (int jj = 0; jj < N; ++jj) {
-                        const double sre = C[a*N + jj].re + X[jj].re, sim = C[a*N + jj].im + X[jj].im;
-                        C[a*N + jj] = {fma(ph.re, sre, ph.im*sim), fma(ph.re, sim, -(ph.im*sre))};
-                    }
+                    summand2(Rg, a, rstride, Lam, X);
+                    fold2(ph, X, C, a);
                 }
-                // Lam <- L_k Lam
-                {
-                    const double* Lsrc = Lpulse + static_cast<size_t>(k)*LN + vzero;
-                    double Ln[LN];
-#pragma unroll
-                    for (int i = 0; i < N; ++i)
-#pragma unroll
-                        for (int l = 0; l < N; ++l) {
-                            double acc = 0.0;
-#pragma unroll
-                            for (int m = 0; m < N; ++m) acc = fma(Lsrc[i*N + m], Lam[m*N + l], acc);
-                            Ln[i*N + l] = acc;
-                        }
-#pragma unroll
-                    for (int e = 0; e < LN; ++e) Lam[e] = Ln[e];
-                }
+                advance2(Lpulse + static_cast<size_t>(k)*LN + vzero, Lam);
                 // the epilogue of this position
                 double* pos0 = partial + (static_cast<size_t>(blockIdx.x)*n_index + g)*per_position;
 #pragma unroll
@@ -193,17 +107,7 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk2_kernel(
                     cplx E[N];
 #pragma unroll
                     for (int jj = 0; jj < N; ++jj) E[jj] = C[a*N + jj];
-                    if (closing != nullptr) {
-#pragma unroll
-                        for (int kk = 0; kk < N; ++kk) {
-                            const cplx v = Rc[(a*N + kk)*rstride];
-#pragma unroll
-                            for (int jj = 0; jj < N; ++jj) {
-                                E[jj].re = fma(v.re, Lam[kk*N + jj], E[jj].re);
-                                E[jj].im = fma(v.im, Lam[kk*N + jj], E[jj].im);
-                            }
-                        }
-                    }
+                    if (closing != nullptr) add_summand2(Rc, a, rstride, Lam, E);
 #pragma unroll
                     for (int s = 0; s < kSpectra; ++s) {
                         if (sp0 + s >= n_spectra) continue;
@@ -219,14 +123,14 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk2_kernel(
                             }
 #pragma unroll
                             for (; e < 16; ++e) v[e] = 0.0;
-                            const double sum = wave_sums<16>(v, lane);
+                            const double sum = wave_sums<16, false>(v, lane);
                             if (stores2) o[tk*N + tl] = sum;
                         } else {
                             double v[N];
 #pragma unroll
                             for (int kk = 0; kk < N; ++kk)
                                 v[kk] = wt[a][s]*fma(E[kk].re, E[kk].re, E[kk].im*E[kk].im);
-                            const double sum = wave_sums<N>(v, lane);
+                            const double sum = wave_sums<N, false>(v, lane);
                             if (stores1) o[lane >> 4] = sum;
                         }
                     }
@@ -236,14 +140,7 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk2_kernel(
     }
 }
 
-size_t staged2_lds_bytes(int T, int A) {
-    return static_cast<size_t>(T)*(A*kN2 + 1)*64*sizeof(cplx);
-}
-
 // ---- d = 4 -------------------------------------------------------------------------------------------------------
-constexpr int kN = 16;
-constexpr int seq4_tiles(int A) { return A <= 2 ? 4 : 2; }             // (as sequences_d4.hip)
-
 template <int A, bool STAGED>
 __global__ __launch_bounds__(64*kWaves) void seqpre_walk4_kernel(
     const cplx* __restrict__ phases, const cplx* const* __restrict__ Rtab, const double* __restrict__ Lpulse,
@@ -262,46 +159,18 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk4_kernel(
     const int c = lane & 15, q = lane >> 4;
     const int w0 = blockIdx.x*WT;
     const int sp0 = blockIdx.z*kSpectra;
-    // the weights of the block's frequencies first ([kSpectra][A][WT], 0 beyond W and for what is not selected), the
-    // staged tables behind them
-    double* Ws = reinterpret_cast<double*>(lds_raw);
+    double* Ws = reinterpret_cast<double*>(lds_raw);                                      // [kSpectra][A][WT]
     cplx* Rs = reinterpret_cast<cplx*>(lds_raw + kSpectra*A*WT*sizeof(double));           // [T][ROWS][WT]
     cplx* Ps = Rs + static_cast<size_t>(T)*ROWS*WT;                                       // [T][WT]
     int sel[A];
 #pragma unroll
-    for (int a = 0; a < A; ++a) {
-        sel[a] = -1;
-        for (int i = n_idx - 1; i >= 0; --i)
-            if (idx[i] == a) sel[a] = i;
-    }
-    for (int e = threadIdx.x; e < kSpectra*A*WT; e += blockDim.x) {
-        const int x = e % WT, a = (e / WT) % A, s = e / (WT*A);
-        int i = -1;
-        for (int m = n_idx - 1; m >= 0; --m)
-            if (idx[m] == a) i = m;
-        Ws[e] = (i >= 0 && sp0 + s < n_spectra && w0 + x < W)
-                    ? weight_row(scale, s_ndim, n_idx, sp0 + s, i, W)[w0 + x].re : 0.0;
-    }
-    if (STAGED) {
-        const int x = lane % WT, wl = min(w0 + x, W - 1);
-        for (int e = wave*(64/WT) + lane/WT; e < T*ROWS; e += n_waves*(64/WT)) {
-            const int k = e / ROWS, r = e % ROWS;
-            Rs[static_cast<size_t>(e)*WT + x] = Rtab[k][static_cast<size_t>(r)*W + wl];
-        }
-        for (int k = wave*(64/WT) + lane/WT; k < T; k += n_waves*(64/WT))
-            Ps[k*WT + x] = phases[static_cast<size_t>(k)*W + wl];
-    }
+    for (int a = 0; a < A; ++a) sel[a] = selected(idx, n_idx, a);
+    stage_weights4<A, kSpectra, WT>(Ws, scale, s_ndim, n_spectra, idx, n_idx, sp0, w0, W);
+    if (STAGED) stage_tables4<ROWS, WT>(Rs, Ps, phases, Rtab, T, W, w0, lane, wave, n_waves);
     __syncthreads();
-    // columns of the table reads: as A operand the frequency is 16 t + c, in a D tile 16 t + q + 4 r
     size_t colA[TILES], colD[TILES][4];
-#pragma unroll
-    for (int t = 0; t < TILES; ++t) {
-        colA[t] = STAGED ? size_t(16*t + c) : size_t(min(w0 + 16*t + c, W - 1));
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            colD[t][r] = STAGED ? size_t(16*t + q + 4*r) : size_t(min(w0 + 16*t + q + 4*r, W - 1));
-    }
-    const size_t rstride = STAGED ? WT : static_cast<size_t>(W);
+    columns4<STAGED>(colA, colD, w0, W, c, q);
+    const size_t rstride = row_stride4<WT, STAGED>(W);
     const size_t tile = mode == 2 ? N*N : N;
     const size_t per_position = static_cast<size_t>(n_spectra)*n_idx*tile;
     const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
@@ -321,48 +190,25 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk4_kernel(
         for (int r = 0; r < 4; ++r) Lam[r] = q + 4*r == c ? 1.0 : 0.0;
         for (int c0 = g_begin; c0 < g_end; c0 += 64) {
             const int c1 = min(g_end, c0 + 64);
-            const int my_index = c0 + lane < c1 ? index[c0 + lane] : 0;
-            const int my_closing = (closing != nullptr && c0 + lane < c1) ? closing[c0 + lane] : 0;
+            const int my_index = chunk_gates(index, true, c0, c1, lane);
+            const int my_closing = chunk_gates(closing, closing != nullptr, c0, c1, lane);
             for (int g = c0; g < c1; ++g) {
-                const int k = __builtin_amdgcn_readlane(my_index, g - c0);
-                const int kc = __builtin_amdgcn_readlane(my_closing, g - c0);
-                const cplx* Rg = STAGED ? Rs + static_cast<size_t>(k)*ROWS*WT : Rtab[k];
-                const cplx* Rc = STAGED ? Rs + static_cast<size_t>(kc)*ROWS*WT : Rtab[kc];
-                const cplx* Pg = STAGED ? Ps + k*WT : phases + static_cast<size_t>(k)*W;
+                const int k = gate_at(my_index, g - c0), kc = gate_at(my_closing, g - c0);
+                const cplx* Rg = gate_rows4<ROWS, WT, STAGED>(Rs, Rtab, k);
+                const cplx* Rc = gate_rows4<ROWS, WT, STAGED>(Rs, Rtab, kc);
+                const cplx* Pg = gate_phases4<WT, STAGED>(Ps, phases, k, W);
 #pragma unroll
                 for (int t = 0; t < TILES; ++t) {
                     cplx ph[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) ph[r] = Pg[colD[t][r]];
+                    load_phases4(Pg, colD[t], ph);
 #pragma unroll
                     for (int a = 0; a < A; ++a) {
                         if (sel[a] < 0) continue;
-                        // X = R Lam: row = frequency 16 t + q + 4 r, col = basis element c
-                        f64x4 xre = zero, xim = zero;
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-                            const cplx v = Rg[(a*N + q + 4*s)*rstride + colA[t]];
-                            xre = __builtin_amdgcn_mfma_f64_16x16x4f64(v.re, Lam[s], xre, 0, 0, 0);
-                            xim = __builtin_amdgcn_mfma_f64_16x16x4f64(v.im, Lam[s], xim, 0, 0, 0);
-                        }
-                        // C <- conj(p) (C + X)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const double sre = Cre[a][t][r] + xre[r], sim = Cim[a][t][r] + xim[r];
-                            Cre[a][t][r] = fma(ph[r].re, sre, ph[r].im*sim);
-                            Cim[a][t][r] = fma(ph[r].re, sim, -(ph[r].im*sre));
-                        }
+                        fold4(ph, add_summand4(Rg + (a*N + q)*rstride + colA[t], rstride, Lam, {zero, zero}), Cre[a][t],
+                              Cim[a][t]);
                     }
                 }
-                // Lam <- L_k Lam
-                {
-                    const double* Lsrc = Lpulse + static_cast<size_t>(k)*N*N + c*N + q;
-                    f64x4 Ln = zero;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        Ln = __builtin_amdgcn_mfma_f64_16x16x4f64(Lsrc[4*r], Lam[r], Ln, 0, 0, 0);
-                    Lam = Ln;
-                }
+                advance4(Lpulse + static_cast<size_t>(k)*N*N + c*N + q, Lam);
                 // the epilogue of this position: E = C (+ R_c Lam), then its weighted Gram matrix or squares
                 double* pos0 = partial + (static_cast<size_t>(blockIdx.x)*n_index + g)*per_position;
 #pragma unroll
@@ -378,30 +224,18 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk4_kernel(
                     }
 #pragma unroll
                     for (int t = 0; t < TILES; ++t) {
-                        f64x4 ere = Cre[a][t], eim = Cim[a][t];
-                        if (closing != nullptr) {
-#pragma unroll
-                            for (int s = 0; s < 4; ++s) {
-                                const cplx v = Rc[(a*N + q + 4*s)*rstride + colA[t]];
-                                ere = __builtin_amdgcn_mfma_f64_16x16x4f64(v.re, Lam[s], ere, 0, 0, 0);
-                                eim = __builtin_amdgcn_mfma_f64_16x16x4f64(v.im, Lam[s], eim, 0, 0, 0);
-                            }
-                        }
+                        tile4 E = {Cre[a][t], Cim[a][t]};
+                        if (closing != nullptr) E = add_summand4(Rc + (a*N + q)*rstride + colA[t], rstride, Lam, E);
 #pragma unroll
                         for (int s = 0; s < kSpectra; ++s) {
                             if (sp0 + s >= n_spectra) continue;
                             const double* wrow = Ws + (s*A + a)*WT + 16*t + q;
                             if (mode == 2) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const double wgt = wrow[4*r];
-                                    Gre[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(ere[r], wgt*ere[r], Gre[s], 0, 0, 0);
-                                    Gim[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(eim[r], wgt*eim[r], Gim[s], 0, 0, 0);
-                                }
+                                gram4(wrow, E, E.re, E.im, Gre[s], Gim[s]);
                             } else {
 #pragma unroll
                                 for (int r = 0; r < 4; ++r)
-                                    dsum[s] = fma(wrow[4*r], fma(ere[r], ere[r], eim[r]*eim[r]), dsum[s]);
+                                    dsum[s] = fma(wrow[4*r], fma(E.re[r], E.re[r], E.im[r]*E.im[r]), dsum[s]);
                             }
                         }
                     }
@@ -424,13 +258,6 @@ __global__ __launch_bounds__(64*kWaves) void seqpre_walk4_kernel(
             }
         }
     }
-}
-
-size_t weights4_lds_bytes(int A) {
-    return static_cast<size_t>(kSpectra)*A*16*seq4_tiles(A)*sizeof(double);
-}
-size_t staged4_lds_bytes(int T, int A) {
-    return static_cast<size_t>(T)*(A*kN + 1)*16*seq4_tiles(A)*sizeof(cplx);
 }
 
 // out (n_spectra, n_index, n_idx[, N[, N]]): the frequency blocks of partial (blocks, n_index, n_spectra, n_idx, N[, N])
@@ -468,7 +295,7 @@ __global__ __launch_bounds__(256) void seqpre_reduce_kernel(const double* __rest
 }  // namespace
 
 int sequence_prefix_block_width(int d, int A) {
-    return d == 2 ? 64 : 16*seq4_tiles(A);
+    return block_width(d, A);
 }
 
 int sequence_prefix_spectra_per_walk() {
@@ -476,8 +303,7 @@ int sequence_prefix_spectra_per_walk() {
 }
 
 bool sequence_prefix_staged(int d, int T, int A) {
-    if (d == 2) return staged2_lds_bytes(T, A) <= 150*1024;
-    return staged4_lds_bytes(T, A) + weights4_lds_bytes(A) <= 150*1024;
+    return tables_staged(d, T, A, kSpectra);
 }
 
 hipError_t launch_sequence_prefix(int d, const cplx* phases, const cplx* const* Rtab, const double* Lpulse,
@@ -489,44 +315,22 @@ hipError_t launch_sequence_prefix(int d, const cplx* phases, const cplx* const* 
         (s_ndim != 1 && s_ndim != 2) || (d != 2 && d != 4) || n_index < size_t(P) || n_index > 0x7fffffffull)
         return hipErrorInvalidValue;
     const bool staged = sequence_prefix_staged(d, T, A);
-    const int width = sequence_prefix_block_width(d, A);
-    const int blocks = (W + width - 1)/width;
+    const int blocks = (W + block_width(d, A) - 1)/block_width(d, A);
     const int walks = (n_spectra + kSpectra - 1)/kSpectra;
     if (walks > 65535) return hipErrorInvalidValue;
-    // as launch_sequence_second_order: staged, one block per CU; else a few; never more groups than wavefronts' worth
-    // of sequences
-    long groups = ((staged ? 256L : 1024L) + static_cast<long>(blocks)*walks - 1)/(static_cast<long>(blocks)*walks);
-    groups = std::min(groups, (static_cast<long>(P) + kWaves - 1)/kWaves);
-    groups = std::max(1L, std::min(groups, 65535L));
-    const dim3 grid(blocks, static_cast<unsigned>(groups), walks);
-    const int n_groups = static_cast<int>(groups);
-    auto launch = [&](auto kern, size_t lds) -> hipError_t {
-        if (lds > 48*1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     static_cast<int>(lds));
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(64*kWaves), lds, stream, phases, Rtab, Lpulse, offsets, index, closing,
-                           order, P, static_cast<int>(n_index), T, W, n_groups, scale, s_ndim, n_spectra, idx, n_idx,
-                           mode, partial);
-        return hipGetLastError();
+    const int n_groups = walk_groups(staged, blocks, walks, P);
+    const dim3 grid(blocks, n_groups, walks);
+    const size_t lds = walk_lds_bytes(d, staged, T, A, kSpectra);
+    auto launch = [&](auto kern) {
+        return launch_walk(kern, grid, lds, stream, phases, Rtab, Lpulse, offsets, index, closing, order, P,
+                           static_cast<int>(n_index), T, W, n_groups, scale, s_ndim, n_spectra, idx, n_idx, mode,
+                           partial);
     };
-    hipError_t err = hipErrorInvalidValue;
-#define FFK_SEQPRE(AA)                                                                                              \
-    case AA:                                                                                                        \
-        if (d == 2)                                                                                                 \
-            err = staged ? launch(seqpre_walk2_kernel<AA, true>, staged2_lds_bytes(T, AA))                          \
-                         : launch(seqpre_walk2_kernel<AA, false>, 0);                                               \
-        else                                                                                                        \
-            err = staged ? launch(seqpre_walk4_kernel<AA, true>, staged4_lds_bytes(T, AA) + weights4_lds_bytes(AA)) \
-                         : launch(seqpre_walk4_kernel<AA, false>, weights4_lds_bytes(AA));                          \
-        break;
-    switch (A) {
-        FFK_SEQPRE(1) FFK_SEQPRE(2) FFK_SEQPRE(3) FFK_SEQPRE(4)
-        default: break;
-    }
-#undef FFK_SEQPRE
+    const hipError_t err = for_operators(A, [&](auto AA) {
+        constexpr int a = decltype(AA)::value;
+        if (d == 2) return staged ? launch(seqpre_walk2_kernel<a, true>) : launch(seqpre_walk2_kernel<a, false>);
+        return staged ? launch(seqpre_walk4_kernel<a, true>) : launch(seqpre_walk4_kernel<a, false>);
+    });
     if (err != hipSuccess) return err;
     const int N = d*d;
     const size_t out_tile = mode == 2 ? size_t(N)*N : mode == 1 ? size_t(N) : 1;

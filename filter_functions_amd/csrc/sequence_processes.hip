@@ -25,7 +25,7 @@
 //                             wrote, no block barrier.  Real and imaginary products go to accumulators of their own
 //                             and are added at the end; spectra beyond the first reuse the transposed R and only
 //                             change the weights.
-#include "ffk_internal.h"
+#include "sequence_walk.h"
 
 namespace ffk {
 namespace {
@@ -37,10 +37,8 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// the row of the weights of selected operator i under spectrum sp: (n_spectra, W) or (n_spectra, n_idx, W)
-__device__ __forceinline__ const cplx* weight_row(const cplx* scale, int s_ndim, int n_idx, int sp, int i, int W) {
-    return scale + static_cast<size_t>(s_ndim == 1 ? sp : sp*n_idx + i)*W;
-}
+using seqwalk::seq4_tiles;
+using seqwalk::weight_row;
 
 // ---- d = 2 -------------------------------------------------------------------------------------------------------
 constexpr int kSeqN = 4;
@@ -158,7 +156,6 @@ constexpr int kN = 16;
 constexpr int kRuleWaves = 4;
 constexpr int kPad = 17;                                   // doubles of a row of the transposition tiles
 constexpr int kScratch = 2*kN*kPad;                        // doubles of one wavefront's two tiles (4352 bytes)
-constexpr int seq4_tiles(int A) { return A <= 2 ? 4 : 2; }             // (as sequences_d4.hip)
 
 template <int A, bool STAGED>
 __global__ __launch_bounds__(64*kRuleWaves) void sequences4_gamma_kernel(

@@ -19,7 +19,7 @@
 //                             matrix R is never written
 #include <algorithm>
 
-#include "ffk_internal.h"
+#include "sequence_walk.h"
 
 namespace ffk {
 namespace {
@@ -116,9 +116,7 @@ __global__ __launch_bounds__(kFrontThreads) void sequences4_front_kernel(
     }
 }
 
-// tiles of sixteen frequencies a wavefront walks at once: 64 A accumulator registers at four tiles, which A <= 2
-// affords; A = 3 and 4 take two tiles (32 frequencies), 96 and 128 accumulator registers
-constexpr int seq4_tiles(int A) { return A <= 2 ? 4 : 2; }
+using seqwalk::seq4_tiles;               // tiles of sixteen frequencies a wavefront walks at once
 
 // One block: 16 TILES frequencies and one group of sequences, dealt out as in sequences_rule_kernel (work item j of
 // the sequences sorted by length, longest first, goes to wavefront j mod Q).  Lane (c, q) = (lane & 15, lane >> 4)

@@ -14,8 +14,8 @@ side: the reference's object model, argument checking, caching and exceptions.
 See DESIGN.md for the scope, INTEGRATION.md for the boundary.
 """
 from . import (analytic, basis, batch, batch_gradient, batch_second_order, correlations, expm_batch, gradient, numeric, periodic, periodic_second_order, processes, pulse_sequence, sequences,
-               sequence_prefix_second_order, sequence_prefixes, sequence_processes, sequence_second_order, superoperator,
-               util)
+               sequence_gradient, sequence_prefix_second_order, sequence_prefixes, sequence_processes, sequence_second_order,
+               superoperator, util)
 from .basis import Basis
 from .batch import get_filter_functions, infidelities
 from .batch_gradient import filter_function_derivatives, infidelity_derivatives
@@ -30,6 +30,8 @@ from .periodic_second_order import (periodic_cumulant_functions, periodic_error_
 from .processes import cumulant_functions, decay_amplitudes, error_transfer_matrices
 from .sequences import concatenate_sequences
 from .sequence_correlations import sequence_correlation_infidelities
+from .sequence_gradient import (gate_infidelity_derivatives, sequence_filter_function_derivatives,
+                                sequence_infidelity_derivatives)
 from .sequence_infidelities import sequence_infidelities
 from .sequence_prefixes import (sequence_prefix_decay_amplitudes, sequence_prefix_infidelities,
                                 sequence_prefix_propagators)
@@ -49,13 +51,14 @@ __all__ = ['analytic', 'Basis', 'PulseSequence', 'basis', 'batch', 'batch_gradie
            'correlation_infidelities', 'correlations',
            'concatenate_without_filter_function', 'cumulant_functions', 'decay_amplitudes',
            'error_transfer_matrices', 'error_transfer_matrix', 'expm_batch', 'exponentiate_cumulant_functions', 'extend', 'get_filter_functions', 'gradient', 'infidelities', 'infidelity',
-           'filter_function_derivatives', 'frequency_shifts', 'infidelity_derivative', 'infidelity_derivatives',
+           'filter_function_derivatives', 'frequency_shifts', 'gate_infidelity_derivatives', 'infidelity_derivative', 'infidelity_derivatives',
            'liouville_representation', 'numeric', 'periodic', 'periodic_decay_amplitudes',
            'periodic_cumulant_functions', 'periodic_error_transfer_matrices', 'periodic_filter_functions',
            'periodic_frequency_shifts', 'periodic_infidelities', 'periodic_second_order', 'processes',
            'pulse_sequence', 'remap', 'sequence_correlation_infidelities', 'sequence_correlations',
            'sequence_cumulant_functions', 'sequence_decay_amplitudes',
-           'sequence_error_transfer_matrices', 'sequence_frequency_shifts', 'sequence_infidelities',
+           'sequence_error_transfer_matrices', 'sequence_filter_function_derivatives', 'sequence_frequency_shifts',
+           'sequence_gradient', 'sequence_infidelities', 'sequence_infidelity_derivatives',
            'sequence_prefix_cumulant_functions', 'sequence_prefix_decay_amplitudes',
            'sequence_prefix_error_transfer_matrices', 'sequence_prefix_frequency_shifts',
            'sequence_prefix_infidelities', 'sequence_prefix_propagators', 'sequence_prefix_second_order',

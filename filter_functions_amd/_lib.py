@@ -8,7 +8,7 @@ a GPU.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_long, c_size_t, c_uint, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_long, c_longlong, c_size_t, c_uint, c_void_p
 
 import numpy as np
 
@@ -215,6 +215,12 @@ SIGNATURES = {
     'ffk_batch_filter_function_derivative': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                                      c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                                      c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'ffk_sequence_infidelity_derivatives_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_longlong, c_longlong,
+                                                                       c_int, c_int, c_int, c_int, c_int]),
+    'ffk_sequence_infidelity_derivatives': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                    c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ffk_batch_frequency_shifts_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                               c_int]),
     'ffk_batch_frequency_shifts_chunk': (c_int, [c_int, c_int, c_int, c_int, c_int]),

@@ -599,6 +599,40 @@ hipError_t launch_grad_batch(int P, const double* eigvals, const cplx* eigvecs, 
                              const cplx* c_opers, int H, const double* ratio, const double* dt, const double* t,
                              int G, int d, const cplx* scale, int s_ndim, cplx* rec, cplx* totals, cplx* ytot,
                              double* partial, double* dF, double* dI, hipStream_t stream);
+// The pieces of that pass which sequence_gradient.hip runs over a gate set, a gate standing where a pulse stands: the
+// records of every segment (arguments as above), the sum of the steps of ALL G segments of each pulse -- totals
+// (P, A, d, d, W), one chunk per pulse --, and the reduction of `tiles` rows of partials: out[row] = sum_k
+// partial[k][row] / d, in index order.
+hipError_t launch_grad_batch_records(int P, const double* eigvals, const cplx* eigvecs, const cplx* propagators,
+                                     const cplx* n_opers, int A, const double* n_coeffs, const cplx* c_opers, int H,
+                                     const double* dt, const double* t, int G, int d, cplx* rec, hipStream_t stream);
+hipError_t launch_grad_batch_pulse_totals(int P, const double* omega, int W, const cplx* rec, int G, int d, int A,
+                                          int H, cplx* totals, hipStream_t stream);
+hipError_t launch_grad_batch_reduce(const double* partial, int tiles, size_t rows, int d, double* out,
+                                    hipStream_t stream);
+
+// ---- sequence_gradient.hip (gate sequences as index arrays into one gate set, 2 <= d <= 4, A <= 4, H <= 8) ------
+// The gate set is a batch of T "pulses" of Gmax segments (shorter gates padded with segments of zero duration that
+// are never walked): rec and totals from the launchers above.  U (T, d, d) and tau (T) are the gates' total
+// propagators and durations, gate_segments (T) their true segment counts.  Sequences in CSR form (offsets (P + 1),
+// index), seg_start (P + 1): the number of walked segments before each sequence.  Rows of the outputs: sequence p
+// holds rows [A seg_start[p], A seg_start[p + 1]) as (a, segment); every row has H entries.  dF (rows, H, W) and / or
+// partial (ceil(W / 64), rows, H) (needs scale, from launch_spectral_weights with 1 or A rows), either may be NULL.
+// One launch, whatever P.
+bool sequence_gradient_supported(int T, int Gmax, int P, int W, int A, int H, int d);
+hipError_t launch_sequence_gradient_walk(const double* omega, int W, const cplx* rec, const cplx* totals,
+                                         const cplx* U, const double* tau, const int32_t* gate_segments, int Gmax,
+                                         const int32_t* offsets, const int32_t* index, const int64_t* seg_start,
+                                         int P, int d, int A, int H, const cplx* scale, int s_ndim, double* dF,
+                                         double* partial, hipStream_t stream);
+// out (T, A, Gmax, H)[k, a, s, h] = start[k, a, s, h] + sum over the occurrences o of gate k, in list order (occ_offsets (T + 1)), of
+// occ_weight[o] dI[(occ_row[o] + a occ_length[o] + s) H + h]: occ_row = A seg_start[p] + the segments of sequence p
+// before the position, occ_length the segments of sequence p, added one after the other.  Entries with s >=
+// gate_segments[k] keep their start.  One thread per entry, no atomics.
+hipError_t launch_sequence_gradient_gather(const double* dI, const int32_t* occ_offsets, const int64_t* occ_row,
+                                           const int32_t* occ_length, const double* occ_weight,
+                                           const int32_t* gate_segments, int T, int Gmax, int A, int H,
+                                           const double* start, double* out, hipStream_t stream);
 
 // B (W,A,d,d) = B^(0) + sum_g phases[g-1] P_{g-1}^dag B^(g) P_{g-1}; atomic (G,W,A,d,d), props (G-1,d,d)
 hipError_t launch_noise_ops_from_atomic(const cplx* phases, const cplx* atomic, const cplx* props,

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "ffk_internal.h"
+#include "grad_walk.h"
 
 namespace ffk {
 
@@ -37,12 +38,10 @@ int grad_batch_chunk(int G, int d, int W) {
 
 namespace {
 
-// ---- record of one segment, in complex numbers: a header of 1 + d2 [as doubles: dt_s, t_s, W_mn (d2), 
-//      derivative_integral_rcp(W_mn, dt_s) (d2)], then [T (d2)] [Bbar (A d2)] [Abar (H d2)] [E (H d2)] ------------------------------------
-__host__ __device__ inline size_t record_header(int d) { return static_cast<size_t>(1 + d*d); }
-__host__ __device__ inline size_t record_elems(int d, int A, int H) {
-    return record_header(d) + static_cast<size_t>(1 + A + 2*H)*d*d;
-}
+using gradwalk::integrals_and_half_step;
+using gradwalk::record_elems;
+using gradwalk::record_header;
+using gradwalk::step_entry;
 
 __global__ __launch_bounds__(64) void gradb_prologue_kernel(
     const double* __restrict__ eigvals, const cplx* __restrict__ eigvecs, const cplx* __restrict__ propagators,
@@ -122,38 +121,6 @@ __global__ __launch_bounds__(64) void gradb_prologue_kernel(
     }
 }
 
-// I1[e] = I1(w + W_e) into the lane's LDS column, then Z = (Bbar o I1) T into the lane's second column
-template <int D>
-__device__ __forceinline__ void integrals_and_half_step(double om, double dts, const double* __restrict__ dE,
-                                                        const cplx* __restrict__ Ts, const cplx* __restrict__ Bs,
-                                                        cplx* __restrict__ I1, cplx* __restrict__ Z) {
-    constexpr int D2 = D*D;
-#pragma unroll 1
-    for (int e = 0; e < D2; ++e) I1[e*64] = first_order_integral(om, dE[e], dts);
-#pragma unroll 1
-    for (int m = 0; m < D; ++m) {
-        cplx X[D];
-#pragma unroll
-        for (int n = 0; n < D; ++n) X[n] = cmul(Bs[m*D + n], I1[(m*D + n)*64]);
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            cplx acc = {0.0, 0.0};
-#pragma unroll
-            for (int n = 0; n < D; ++n) cmac(acc, X[n], Ts[n*D + j]);
-            Z[(m*D + j)*64] = acc;
-        }
-    }
-}
-// entry [i][j] of the step e^{i w t_s} T^dag Z
-template <int D>
-__device__ __forceinline__ cplx step_entry(const cplx* __restrict__ Ts, const cplx* __restrict__ Z, cplx ph, int i,
-                                           int j) {
-    cplx acc = {0.0, 0.0};
-#pragma unroll
-    for (int m = 0; m < D; ++m) cmac_conj(acc, Ts[m*D + i], Z[(m*D + j)*64]);
-    return cmul(ph, acc);
-}
-
 template <int D>
 __global__ __launch_bounds__(64) void gradb_totals_kernel(const double* __restrict__ omega, int W,
                                                           const cplx* __restrict__ rec, int G, int A, int H, int L,
@@ -224,18 +191,8 @@ __global__ __launch_bounds__(64) void grad_batch_kernel(
     int G, int A, int H, int L, int C, int P, double* __restrict__ dF, double* __restrict__ partial) {
     constexpr int D2 = D*D;
     extern __shared__ unsigned char smem[];
-    cplx* head = reinterpret_cast<cplx*>(smem);            // the record's header: dt_s, t_s,
-    const double* hdr = reinterpret_cast<const double*>(smem);
-    const double* dE = hdr + 2;                            // [D2]  W_mn
-    const double* inv = dE + D2;                           // [D2]  derivative_integral_rcp(W_mn, dt)
-    cplx* Ts = head + 1 + D2;                              // [D2]
-    cplx* Bs = Ts + D2;                                    // [D2]   (this block's operator)
-    cplx* As = Bs + D2;                                    // [H][D2]
-    cplx* Es = As + H*D2;                                  // [H][D2]
-    double* sec = reinterpret_cast<double*>(Es + H*D2);    // [H][64]  per-lane Re tr(E_h comm)
     const int lane = threadIdx.x;
-    cplx* I1 = reinterpret_cast<cplx*>(sec + H*64) + lane; // [D2][64] per-lane columns
-    cplx* Wa = I1 + D2*64;                                 // [D2][64] Z = (Bbar o I1) T first, then W_a
+    const gradwalk::SegmentLds<D> lds(smem, H, lane);
     const int c = blockIdx.x / A, a = blockIdx.x % A, p = blockIdx.y, tile = blockIdx.z;
     const int w = tile*64 + lane;
     const bool valid = w < W;
@@ -267,105 +224,18 @@ __global__ __launch_bounds__(64) void grad_batch_kernel(
     if (partial) partial += static_cast<size_t>(tile)*P*A*G*H + row0;
 #pragma unroll 1
     for (int s = c*L; s < s_end; ++s) {
-        const cplx* r = rec + s*rs;
-        __syncthreads();
-        if (lane < 1 + 2*D2) head[lane] = r[lane];
-        if (lane < D2) Bs[lane] = r[b_off + lane];
-        for (int e = lane; e < 2*H*D2; e += 64) As[e] = r[ae_off + e];   // Abar, E
-        __syncthreads();
-        const double dts = hdr[0];
-        const cplx ph = cexp(om*hdr[1]);
-        integrals_and_half_step<D>(om, dts, dE, Ts, Bs, I1, Wa);
-        // Ycum += step; explicit sensitivity term 2 Re tr(Ytot^dag step)
-        double tr_step = 0.0;
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const cplx st = step_entry<D>(Ts, Wa, ph, i, j);
-                Yq[i*D + j].re += st.re;
-                Yq[i*D + j].im += st.im;
-                tr_step += Yd[j*D + i].re*st.re - Yd[j*D + i].im*st.im;
-            }
-        tr_step *= 2.0;
-        // (II): sec[h] = Re tr(E_h [Yd, Ycum])
-        for (int h = 0; h < H; ++h) sec[h*64 + lane] = 0.0;
-#pragma unroll
-        for (int x = 0; x < D; ++x)
-#pragma unroll
-            for (int y = 0; y < D; ++y) {
-                cplx cm = {0.0, 0.0};                      // comm[y][x]
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    cmac(cm, Yd[y*D + k], Yq[k*D + x]);
-                    const cplx q = cmul(Yq[y*D + k], Yd[k*D + x]);
-                    cm.re -= q.re;
-                    cm.im -= q.im;
-                }
-                for (int h = 0; h < H; ++h) {
-                    const cplx e = Es[h*D2 + x*D + y];
-                    sec[h*64 + lane] += e.re*cm.re - e.im*cm.im;
-                }
-            }
-        // Wa = T Yd T^dag, row by row (Z is used up)
-#pragma unroll
-        for (int x = 0; x < D; ++x) {
-            cplx row[D];                                   // (T Yd)[x][:]
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                cplx acc = {0.0, 0.0};
-#pragma unroll
-                for (int j = 0; j < D; ++j) cmac(acc, Ts[x*D + j], Yd[j*D + k]);
-                row[k] = acc;
-            }
-#pragma unroll
-            for (int y = 0; y < D; ++y) {
-                cplx acc = {0.0, 0.0};
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const cplx ty = Ts[y*D + k];
-                    cmac(acc, row[k], cplx{ty.re, -ty.im});
-                }
-                Wa[(x*D + y)*64] = acc;
-            }
-        }
-#pragma unroll 1
-        for (int h = 0; h < H; ++h) {
-            const cplx* Ab = As + h*D2;
-            cplx first = {0.0, 0.0};
-#pragma unroll 1
-            for (int x = 0; x < D; ++x)
-#pragma unroll 1
-                for (int y = 0; y < D; ++y) {
-                    cplx g = {0.0, 0.0};                   // G_xy (grad.hip)
-                    const cplx iyx = I1[(y*D + x)*64];
-#pragma unroll
-                    for (int n = 0; n < D; ++n) {
-                        const cplx iyn = I1[(y*D + n)*64];
-                        const cplx j1 = derivative_integral(om + dE[y*D + n], dE[n*D + x],
-                                                            inv[n*D + x], dts, iyn, iyx);
-                        cmac(g, cmul(Bs[y*D + n], Ab[n*D + x]), j1);
-                        const cplx inx = I1[(n*D + x)*64];
-                        const cplx j2 = derivative_integral(om + dE[n*D + x], dE[y*D + n],
-                                                            inv[y*D + n], dts, inx, iyx);
-                        const cplx ab = cmul(Ab[y*D + n], Bs[n*D + x]);
-                        cmac(g, cplx{-ab.re, -ab.im}, j2);
-                    }
-                    cmac(first, Wa[(x*D + y)*64], g);
-                }
-            const cplx pf = cmul(ph, first);               // 2 Re(-i ph first) = 2 Im(ph first)
-            double val = 2.0*pf.im - 2.0*sec[h*64 + lane];
+        lds.load(rec + s*rs, b_off, ae_off, H, lane);
+        gradwalk::segment_terms<D>(lds, om, H, lane, Yd, Yq, [&](int h, double val, double tr_step) {
             if (ratio) val += ratio[static_cast<size_t>(h)*G + s]*tr_step;
             const size_t row = static_cast<size_t>(s)*H + h;
             if (dF != nullptr && valid) dF[row*W] = val;
             if (partial != nullptr) {
                 double sum = val*weight;                   // (lanes past W: weight 0)
                 if (!valid) sum = 0.0;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+                sum = gradwalk::lane_sum(sum);
                 if (lane == 0) partial[row] = sum;
             }
-        }
+        });
     }
 }
 
@@ -394,8 +264,7 @@ hipError_t launch_walkers(const double* omega, int W, const cplx* rec, const dou
                        totals, C, slab, ytot);
     err = hipGetLastError();
     if (err != hipSuccess) return err;
-    const size_t lds = size_t(1 + D*D)*sizeof(cplx) + size_t(2 + 2*H)*D*D*sizeof(cplx) +
-                       size_t(H)*64*sizeof(double) + 2*size_t(D*D)*64*sizeof(cplx);
+    const size_t lds = gradwalk::segment_lds_bytes(D, H);
     hipLaunchKernelGGL((grad_batch_kernel<D>), grid, dim3(64), lds, stream, omega, W, rec, totals, ytot, ratio, scale, s_ndim, G, A, H, L, C, P, dF, partial);
     return hipGetLastError();
 }
@@ -441,6 +310,41 @@ hipError_t launch_grad_batch(int P, const double* eigvals, const cplx* eigvecs, 
     if ((rows + 255)/256 > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gradb_reduce_kernel, dim3(static_cast<unsigned>((rows + 255)/256)), dim3(256), 0, stream,
                        partial, (W + 63)/64, rows, 1.0/d, dI);
+    return hipGetLastError();
+}
+
+// ---- the pieces of the pass that sequence_gradient.hip runs over a gate set (one "pulse" per gate) ----------------
+hipError_t launch_grad_batch_records(int P, const double* eigvals, const cplx* eigvecs, const cplx* propagators,
+                                     const cplx* n_opers, int A, const double* n_coeffs, const cplx* c_opers, int H,
+                                     const double* dt, const double* t, int G, int d, cplx* rec, hipStream_t stream) {
+    if (P < 1 || P > 65535 || G < 1 || G > 65535 || d < 2 || d > 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gradb_prologue_kernel, dim3(G, P), dim3(64), 0, stream, eigvals, eigvecs, propagators, n_opers,
+                       n_coeffs, c_opers, dt, t, G, d, A, H, rec);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_batch_pulse_totals(int P, const double* omega, int W, const cplx* rec, int G, int d, int A,
+                                          int H, cplx* totals, hipStream_t stream) {
+    if (P < 1 || P > 65535 || (W + 63)/64 > 65535) return hipErrorInvalidValue;
+    const dim3 grid(A, P, (W + 63)/64);
+    switch (d) {
+#define FFK_GRADB_CASE(D)                                                                                          \
+    case D:                                                                                                        \
+        hipLaunchKernelGGL((gradb_totals_kernel<D>), grid, dim3(64), 0, stream, omega, W, rec, G, A, H, G, 1,      \
+                           totals);                                                                                \
+        break;
+        FFK_GRADB_CASE(2) FFK_GRADB_CASE(3) FFK_GRADB_CASE(4)
+#undef FFK_GRADB_CASE
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_batch_reduce(const double* partial, int tiles, size_t rows, int d, double* out,
+                                    hipStream_t stream) {
+    if (rows < 1 || (rows + 255)/256 > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gradb_reduce_kernel, dim3(static_cast<unsigned>((rows + 255)/256)), dim3(256), 0, stream,
+                       partial, tiles, rows, 1.0/d, out);
     return hipGetLastError();
 }
 

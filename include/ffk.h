@@ -566,6 +566,48 @@ int ffk_batch_filter_function_derivative(int P, const double* eigvals, const dou
                                          int s_ndim, double* filter_function_derivative,
                                          double* infidelity_derivative);
 
+/* ---- sequence gradient: P gate sequences, index arrays into ONE gate set, in ONE pass
+ *      (ff.sequence_infidelity_derivatives / ff.sequence_filter_function_derivatives / ff.gate_infidelity_derivatives)
+ * The derivatives of the filter function / infidelity of the concatenated sequences by the amplitudes of every
+ * segment that stands in them, 2 <= d <= 4, A <= 4, H <= 8, T, P, Gmax <= 65535.  The gate set: T gates with the same
+ * noise operators n_opers (A, d, d) and control operators c_opers (H, d, d), gate k with gate_segments[k] <= Gmax
+ * segments, every per-gate array gate-major and padded to Gmax segments of ZERO duration: eigvals (T, Gmax, d) (0),
+ * eigvecs (T, Gmax, d, d) (identity), propagators (T, Gmax + 1, d, d) (the last one repeated: row Gmax is the gate's
+ * total propagator), n_coeffs (T, A, Gmax) (0), dt (T, Gmax) (0).  The sequences in CSR form: offsets (P + 1) int32
+ * from 0, strictly increasing, index (offsets[P]) int32 in [0, T).  omega (W,), spectrum (W,) or (A, W) c128
+ * (s_ndim 1, 2).  Sequence p has G_p = sum of gate_segments over its positions segments, and S_p = sum of G_q, q < p,
+ * stand before it.  Outputs, any may be NULL but not all:
+ *   filter_function_derivative  sequence p at S_p A H W doubles: (A, G_p, H, W)
+ *   infidelity_derivative       sequence p at S_p A H doubles: (A, G_p, H)
+ *   gate_infidelity_derivative  (T, A, Gmax, H), IN and out: to what entry [k] holds the call adds, over the occurrences
+ *                               of gate k -- occ_offsets (T + 1) int32, then per occurrence occ_sequence and
+ *                               occ_position, int32, every position named once under its gate --, one after the other
+ *                               in list order, weights[p] times the position's (A, G_k, H) slice of sequence p's
+ *                               infidelity derivative (consecutive passes thus give one sequential sum); rows past
+ *                               gate_segments[k] are kept.  One thread per entry, no atomics; the sequences'
+ *                               derivatives stay on the device.
+ * The kernels work in the frame of the current position, in which one record per gate segment serves every position
+ * and sequence (csrc/sequence_gradient.hip); nothing of the size of a sequence is formed, and with only infidelity
+ * derivatives requested the filter-function derivative is never stored.  One H2D copy from a pinned staging block, a
+ * fixed number of launches whatever P, one D2H copy per requested output.  A sequence's result is the same bits
+ * whatever else is in the pass.  Bad arguments (an index outside [0, T), an empty sequence, W < 1, s_ndim not 1 or 2
+ * with an infidelity output, ...) return FFK_EINVAL before anything touches the device.
+ * ..._workspace_bytes runs without a GPU: device bytes of a pass over n_index positions and n_segments walked
+ * segments in all (exactly linear in n_segments, an upper bound; 0 for a shape the pass does not take); the call
+ * reserves them in the library's arena itself.                                                                  */
+size_t ffk_sequence_infidelity_derivatives_workspace_bytes(int T, int Gmax, int P, long long n_index,
+                                                           long long n_segments, int W, int A, int H, int d,
+                                                           int want_dF);
+int ffk_sequence_infidelity_derivatives(int T, int Gmax, const int32_t* gate_segments, const double* eigvals,
+                                        const double* eigvecs, const double* propagators, const double* n_opers,
+                                        int A, const double* n_coeffs, const double* c_opers, int H, const double* dt,
+                                        int d, const int32_t* offsets, const int32_t* index, int P,
+                                        const double* omega, int W, const double* spectrum, int s_ndim,
+                                        const int32_t* occ_offsets, const int32_t* occ_sequence,
+                                        const int32_t* occ_position, const double* weights,
+                                        double* filter_function_derivative, double* infidelity_derivative,
+                                        double* gate_infidelity_derivative);
+
 /* ffk_frequency_shifts_from_scratch for P pulses of one shape at once, 1 <= P <= 65535, without the second-order
  * filter function in memory.  Per-pulse arrays are pulse-major with a leading axis P, as in
  * ffk_batch_filter_function_derivative; omega (W,), basis (N, d, d), spectrum ((W,), (n_idx, W) or (n_idx, n_idx, W)
